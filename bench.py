@@ -4,7 +4,9 @@
 Contract (driver): `python bench.py --gpus N --steps K --warmup W`; for N > 1 it is launched with torch.distributed.run, one
 rank per GPU. One step = one pass of the hot path over one batch of rays that is already resident in HBM:
 enarf_render_step_fwd = one pre-march launch (part frames + modulated MLP weights, NCHW -> channel-last feature planes, ray
-set-up) + the fused ray march (in-kernel importance sampling). Rank 0 prints ONE JSON line.
+set-up) + the fused ray march (in-kernel importance sampling). Rank 0 prints ONE JSON line; `ms_per_step` is the wall time
+of one of the K timed steps. `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32, at most
+64 MB in all); the inputs are seeded, so the same arguments give the same inputs in every run.
 
 Workloads (BASELINE.json `configs`):
   N = 1   configs[1] "C1": one DSO-style 128x128 frame, Nc 48 + Nf 64 samples/ray, 24 SMPL joints (P = 23 parts), constant
@@ -22,6 +24,7 @@ import json
 import os
 import sys
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -41,6 +44,9 @@ UB_TA_SHAPE_GBS = 32060.0
 L1_BYTES_PER_CLK_PER_CU_ASSUMED = 64.0
 BF16_DENSE_TFLOPS = 2500.0
 C3_GLOBAL_FRAMES = 64
+# --dump-outputs: budget of all arrays together, .npy headers included
+DUMP_BYTES = 64 * 10**6
+DUMP_HEADER_BYTES = 256
 
 
 def parse():
@@ -84,7 +90,7 @@ def parse():
     ap.add_argument("--no-p24", action="store_true", help="skip the extra timed pass with origin_location center+head (P = 24)")
     ap.add_argument("--no-f32", action="store_true", help="skip the extra timed pass with the exact fp32 MLP arithmetic")
     ap.add_argument("--two-streams", action="store_true",
-                    help="add a timed pass over two HIP streams (off by default: +2 % at 300 steps on the build boxes, -3 % in the "
+                    help="add a timed pass over two HIP streams (off by default: +2 %% at 300 steps on the build boxes, -3 %% in the "
                          "driver's 20-step run of round 2 - within the noise of a 5 ms timed region)")
     ap.add_argument("--no-two-streams", action="store_true", help="accepted and ignored (the pass is opt-in since round 3)")
     ap.add_argument("--allow-variant", action="store_true", help="measurement only: permit --variant")
@@ -92,7 +98,38 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-rays", type=int, default=4096, help="rays of the same frame per CPU pass (middle band)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="repeat CPU passes until this much time is spent")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the arrays its caller receives) as "
+                         f"DIR/<name>.npy, float32, at most {DUMP_BYTES // 10**6} MB in all (larger arrays as a seeded sample)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def dump_outputs(dirname, named):
+    """Write {name: device tensor} as dirname/<name>.npy (float32) within DUMP_BYTES. Arrays are taken smallest first; one
+    that exceeds its even share of what is left is written as a 1-D sample of its flattened elements at sorted indices
+    drawn from a generator seeded by the name, so the same arguments give the same sample in every build.
+    Returns {name: what was written} for the result line."""
+    os.makedirs(dirname, exist_ok=True)
+    items = sorted(((k, v) for k, v in named.items() if v is not None), key=lambda kv: (kv[1].numel(), kv[0]))
+    left, info = DUMP_BYTES, {}
+    for i, (name, t) in enumerate(items):
+        share = left // (len(items) - i) - DUMP_HEADER_BYTES
+        flat = t.detach().reshape(-1)
+        if flat.numel() * 4 <= share:
+            a = flat.float().cpu().numpy().reshape(tuple(t.shape))
+            sample = None
+        else:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            idx = np.unique(rng.integers(0, flat.numel(), size=share // 4))
+            a = flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy()
+            sample = {"seed": "crc32(name)", "elements": int(a.size), "of": int(flat.numel())}
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        left -= a.nbytes + DUMP_HEADER_BYTES
+        info[name] = {"shape": list(t.shape), "dtype": "float32", "sample": sample}
+    return info
 
 
 def cpu_baseline(scene_cpu, Nc, Nf, n_rays, budget_s):
@@ -255,8 +292,10 @@ def main():
         # a per-frame tri-plane is an activation of the (un-vendored) synthesis network, not a parameter: its gradient stays
         # on the rank; a shared constant tri-plane (DSO style) is a parameter and is reduced with the StyledMLP's
         train_params = ([] if distinct else [tri_param]) + [mlp_params[k] for k in sorted(mlp_params)]
-        g_color = torch.randn(B, 3, n, device=dev)
-        g_mask = torch.randn(B, n, device=dev)
+        gg = torch.Generator(device=dev)
+        gg.manual_seed(7)                  # the same output gradients in every run (--dump-outputs compares runs)
+        g_color = torch.randn(B, 3, n, device=dev, generator=gg)
+        g_mask = torch.randn(B, n, device=dev, generator=gg)
         reducer = sharding.GradientReducer(train_params, world) if dist is not None else None
         local_tri_grads = [None] * n_accum
 
@@ -344,6 +383,7 @@ def main():
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
+    o = gathered = None                # the last timed step's outputs (--dump-outputs)
     t0 = time.perf_counter()
     for i in range(args.steps):
         if args.train_step:
@@ -365,15 +405,15 @@ def main():
                     o = st.run(ops.STEP_MARCH)
                     ev1[i].record()
                 if shard:
-                    gather_outputs(o)
+                    gathered = gather_outputs(o)
             continue
         ops.prepare(d["pose_to_camera"], d["bone_length"], cbl_d, d["z_rend"], mlp, sc["parents"], args.origin,
                     3.0, parts_out=parts, pack_out=pack)
         if not args.cache_triplane:
             ops.triplane_pack(tri, feat_cl)
         ev0[i].record()
-        ops.render_fwd(coord, d["inv_intrinsics"], parts, cpose_d, tri, feat_cl, pack, Nc, Nf, seed=99,
-                       mlp_mode=args.mlp_mode, want_fine=True, early_stop_eps=args.early_stop_eps)
+        o = ops.render_fwd(coord, d["inv_intrinsics"], parts, cpose_d, tri, feat_cl, pack, Nc, Nf, seed=99,
+                           mlp_mode=args.mlp_mode, want_fine=True, early_stop_eps=args.early_stop_eps)
         ev1[i].record()
     torch.cuda.synchronize()
     if dist is not None:
@@ -383,6 +423,19 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: the renderer's outputs (with --shard-frame the
+        # all-gathered frame), or with --train-step the step's gradients; at N > 1 rank 0's share
+        if args.train_step:
+            named = {"grad_" + k: p.grad for k, p in mlp_params.items()}
+            named["grad_tri_plane" + ("_per_frame" if distinct else "")] = (torch.cat(local_tri_grads) if distinct
+                                                                             else tri_param.grad)
+        elif shard:
+            named = {"color": gathered[:, :3], "mask": gathered[:, 3], "disparity": gathered[:, 4]}
+        else:
+            named = {k: getattr(o, k) for k in ("color", "mask", "disparity", "fine_weights", "fine_depth")}
+        dumped = dump_outputs(args.dump_outputs, named)
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in zip(ev0, ev1)]))
     if grouped and not args.train_step:   # the marches alone, from a few extra steps with the two phases issued apart
         ma, mb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -604,6 +657,8 @@ def main():
             out["two_streams"] = two_streams
         if p24 is not None:
             out["p24"] = p24
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(sc, Nc, Nf, min(args.cpu_rays, n), args.cpu_seconds)
         print(json.dumps(out))

@@ -214,13 +214,10 @@ __device__ __forceinline__ float exact_dot3(float a0, float b0, float a1, float 
 }
 
 // ---- bilinear sampling (ATen grid_sampler_2d, bilinear / zeros / align_corners=False) --------------
-#ifndef ENARF_DIAG_NOMUL24      // A/B only
-#define ENARF_DIAG_NOMUL24 0
-#endif
 // row * width for plane coordinates: both far below 2^23 (validated on the host), so the full-rate 24-bit multiply does
 // (v_mul_lo_u32 issues at a quarter of the rate)
 __host__ __device__ __forceinline__ int mul_rc(int a, int b) {
-#if defined(__HIP_DEVICE_COMPILE__) && !ENARF_DIAG_NOMUL24
+#if defined(__HIP_DEVICE_COMPILE__)
     return __mul24(a, b);
 #else
     return a * b;

@@ -72,10 +72,7 @@ static_assert(sizeof(RayRec) == 32, "RayRec");
 // header (u32): [1] rays filed for the march, [2] rays filed as missing every cube, [kWsCountsOff + id] entries in list id, [kWsHeadsOff + 16 * id] queue head of list id -
 // one 64-B slot per head, so that the atomics of different lists do not share a cache line
 constexpr int kQueues = 8;
-#ifndef ENARF_NUM_CLASSES
-#define ENARF_NUM_CLASSES 4
-#endif
-constexpr int kClasses = ENARF_NUM_CLASSES;
+constexpr int kClasses = 4;                                          // cost classes (ray_cost_class)
 constexpr int kWsCountsOff = 16;                                     // u32 index of the list lengths
 constexpr int kNumLists = kQueues * (kClasses + 1);
 __host__ __device__ constexpr int ws_missed_list(int q) { return kQueues * kClasses + q; }
@@ -97,39 +94,22 @@ __device__ __forceinline__ void ws_clear_other_header(void *workspace, int epoch
 }
 // Bands are cut in the padded ray index b * npad + ray (npad = 64 * set-up blocks per image), in multiples of 64, so
 // that the 64 rays of one set-up block always fall into one band: one image -> its eighths; 8 images -> one image per
-// band (XCD). ENARF_IMAGE_BANDS=0 (A/B only) cuts every image into eighths instead, band q of EVERY image in queue q -
-// a smaller texel working set per XCD, but a workgroup then changes image (restages the MLP pack and part frames)
-// B times per cost class: measured slower on every batch (8 frames 2.08 vs 1.80 ms, 16 distinct 4.69 vs 4.42).
-#ifndef ENARF_IMAGE_BANDS
-#define ENARF_IMAGE_BANDS 1
-#endif
+// band (XCD). Cutting every image into eighths instead, band q of EVERY image in queue q, gives a smaller texel working
+// set per XCD, but a workgroup then changes image (restages the MLP pack and part frames) B times per cost class:
+// measured slower on every batch (8 frames 2.08 vs 1.80 ms, 16 distinct 4.69 vs 4.42).
 // rays per set-up block: 256 threads, kSetupLanes lanes per ray (enarf_render.hip ray_setup_block)
-#ifndef ENARF_SETUP_LANES
-#define ENARF_SETUP_LANES 8
-#endif
-constexpr int kSetupLanes = ENARF_SETUP_LANES;
+constexpr int kSetupLanes = 8;
 constexpr int kSetupRays = 256 / kSetupLanes;
 static_assert(kSetupLanes == 4 || kSetupLanes == 8, "set-up lanes per ray");
 __host__ __device__ inline int ws_setup_blocks(int n) { return (n + kSetupRays - 1) / kSetupRays; }
 __host__ __device__ inline long long ws_npad(int n) { return 64ll * ((n + 63) / 64); }
-__host__ __device__ inline long long ws_image_band(int n) {          // rays of one image per band
-    return 64ll * ((ws_npad(n) + 64ll * kQueues - 1) / (64ll * kQueues));
-}
 __host__ __device__ inline long long ws_band_size(int B, int n) {     // capacity of one (band, class) list
-#if ENARF_IMAGE_BANDS
     const long long tot = (long long)B * ws_npad(n);
     return 64ll * ((tot + 64ll * kQueues - 1) / (64ll * kQueues));
-#else
-    return (long long)B * ws_image_band(n);
-#endif
 }
 // band of set-up block `blk` of image b
 __host__ __device__ inline int ws_band_of(int B, int n, int b, int blk) {
-#if ENARF_IMAGE_BANDS
     return (int)(((long long)b * ws_npad(n) + (long long)kSetupRays * blk) / ws_band_size(B, n));
-#else
-    return (int)(((long long)kSetupRays * blk) / ws_image_band(n));
-#endif
 }
 __host__ __device__ inline size_t ws_total_bytes(int B, int n) {
     return ws_list_off((long long)B * n) + (size_t)kNumLists * (size_t)ws_band_size(B, n) * sizeof(uint32_t);
@@ -138,13 +118,7 @@ __host__ __device__ inline size_t ws_total_bytes(int B, int n) {
 // rounds closely: correlation 0.98 on the bench frame): 0 = heaviest
 __device__ __forceinline__ int ray_cost_class(uint32_t cand) {
     const int pc = __popc(cand);
-#if ENARF_NUM_CLASSES == 8        // measured: 4 % slower than 4 classes; 2 classes are on par with 4
-    return pc >= 12 ? 0 : pc >= 10 ? 1 : pc >= 8 ? 2 : pc >= 6 ? 3 : pc >= 4 ? 4 : pc == 3 ? 5 : pc == 2 ? 6 : 7;
-#elif ENARF_NUM_CLASSES == 2
-    return pc >= 6 ? 0 : 1;
-#else
-    return pc >= 10 ? 0 : pc >= 6 ? 1 : pc >= 3 ? 2 : 3;
-#endif
+    return pc >= 10 ? 0 : pc >= 6 ? 1 : pc >= 3 ? 2 : 3;     // measured: 8 classes are 4 % slower, 2 are on par
 }
 
 // wave-private compaction of a part bit set into an LDS list; returns the count
@@ -154,7 +128,7 @@ __device__ __forceinline__ int build_cand_list(int *list, uint32_t set, int lane
 }
 
 // ---- XCD-affine, heaviest-first ray queues --------------------------------------------------------------------------
-// Every image is cut into 8 contiguous row bands (ws_image_band), one per XCD; within a band the set-up pass files every
+// The batch's rays are cut into 8 contiguous bands (ws_band_of), one per XCD; within a band the set-up pass files every
 // live ray (of every image of the batch) under its cost class: kQueues x kClasses lists, each with its own queue head. A workgroup works through the
 // classes heaviest first; within a class it pulls from the band of the XCD it runs on (HW_REG_XCC_ID) and, when that
 // list is drained, from the other bands' lists of the same class in turn.

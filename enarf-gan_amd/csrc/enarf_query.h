@@ -10,65 +10,9 @@
 #pragma once
 #include "enarf_device.h"
 
-#ifndef ENARF_ROUND_SWPIPE     // A/B only: address generation of the next gather round under the last loads of the current
-#define ENARF_ROUND_SWPIPE 0   // one. Measured SLOWER (C1 march 0.235 -> 0.270 ms, both march kernels): DESIGN.md 3.1
-#endif
-#ifndef ENARF_MASK_ROW_PAIRS   // the 4 part-probability taps of a round as 2 eight-byte loads (x0, x0 + 1 are adjacent floats)
-#define ENARF_MASK_ROW_PAIRS 1
-#endif
-#ifndef ENARF_ROUND_PRIO
-#define ENARF_ROUND_PRIO 2
-#endif
-// Work-skipping switches exist only in diagnostic variant builds (tools/build_variant.sh NAME -DENARF_DIAG_ABLATE=k:
-// 4 skips the MLP, 8 replaces the importance draw by a fixed grid); the product library is compiled with 0 and reads no
-// environment variable.
-#ifndef ENARF_DIAG_ABLATE
-#define ENARF_DIAG_ABLATE 0
-#endif
-#ifndef ENARF_DIAG_SCALAR_REDUCE      // A/B only: the round-1 scalar spelling of the tap reduction
-#define ENARF_DIAG_SCALAR_REDUCE 0
-#endif
-#ifndef ENARF_DIAG_GENERAL_TAPS       // 1: fully clamped make_taps in the gather rounds; 0: make_taps_valid
-#define ENARF_DIAG_GENERAL_TAPS 1
-#endif
-#ifndef ENARF_DIAG_TAPCHECK           // diagnosis only: range-check what make_taps_valid would address, march with make_taps
-#define ENARF_DIAG_TAPCHECK 0
-#endif
-
 namespace enarf {
 
-// ENARF_TIMERS=1 (diagnostic builds only, tools/gpu_timers.sh): per-wave cycle sums per phase, returned in counters[0..7]
-#ifndef ENARF_TIMERS
-#define ENARF_TIMERS 0
-#endif
-#if ENARF_TIMERS == 2   // round-internal phases: 0 set-up + issue, 1 mask wait, 2 sigmoid, 3 plane-0 wait, 4 reduce 0/1 + issue 2, 5 plane-2 wait, 6 reduce 2, 7 everything else
-#define TMR(S, k) do { } while (0)
-#define TMR2(S, k) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); (S).tmr[k] += now_ - (S).tmr_t; (S).tmr_t = now_; } while (0)
-#define TMR2_WAIT(S, k, imm) do { __builtin_amdgcn_s_waitcnt(imm); TMR2(S, k); } while (0)
-#elif ENARF_TIMERS == 4  // ray-level stages: 0 header, 1 S2 weights, 2 S2 sampling, 3 S4 heads, 4 S4 scan, 5 S4 sums + stores, 6 barriers, 7 rest
-#define TMR(S, k) do { } while (0)
-#define TMR2(S, k) do { } while (0)
-#define TMR2_WAIT(S, k, imm) do { } while (0)
-#define TMR4(S, k) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); (S).tmr[k] += now_ - (S).tmr_t; (S).tmr_t = now_; } while (0)
-#elif ENARF_TIMERS == 1
-#define TMR2(S, k) do { } while (0)
-#define TMR2_WAIT(S, k, imm) do { } while (0)
-#define TMR(S, k) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); (S).tmr[k] += now_ - (S).tmr_t; (S).tmr_t = now_; } while (0)
-#else
-#define TMR(S, k) do { } while (0)
-#define TMR2(S, k) do { } while (0)
-#define TMR2_WAIT(S, k, imm) do { } while (0)
-#endif
-
-#ifndef TMR4
-#define TMR4(S, k) do { } while (0)
-#endif
-
 struct QueryCtx {
-#if ENARF_TIMERS
-    mutable unsigned long long tmr[8];
-    mutable unsigned long long tmr_t;
-#endif
     const float *mlp;        // LDS: fp32 weights of the MLP pack [PK_W1, PK_B1) (mode F32), else unused
     const short *mlp_h;      // LDS: bf16 section (modes BF16X3 / BF16) or fp16 section (F16X3), else unused
     const float *bias;       // LDS: 144 floats = pack[PK_B1, PK_F32_FLOATS): b1[64] b2[64] b3[16]
@@ -80,10 +24,6 @@ struct QueryCtx {
     int mult_w;              // multiply_density_with_triplane_wieght
     int clamp_mask;          // nerf_params.clamp_mask (sampling.py:46-47)
     float uniform_w;         // > 0: nerf_params.no_selector, every part weighs this (1 / P); 0: part-probability planes
-#if ENARF_DIAG_TAPCHECK
-    unsigned long long *diag;   // counters[5] violations, [6] first: rid | k << 32 | lane << 40 | kind << 48, [7] qx, qy bits
-    unsigned diag_rid;
-#endif
 };
 
 struct QueryDbg {            // optional taps of the point-cloud kernel
@@ -137,17 +77,9 @@ __device__ __forceinline__ void tap4u(const char *__restrict__ base, unsigned la
     }
 }
 
-#ifndef ENARF_PIN
-#define ENARF_PIN 1
-#endif
-#ifndef ENARF_DIAG_HALF_LOADS
-#define ENARF_DIAG_HALF_LOADS 0
-#endif
 // an empty asm the eight values pass through: their computation can be neither sunk below nor hoisted above this point
 __device__ __forceinline__ void pin8(float v[8]) {
-#if ENARF_PIN
     asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]));
-#endif
 }
 
 // tap4u in two halves, so that the loads of one plane can be in flight while another plane is being reduced
@@ -157,32 +89,14 @@ __device__ __forceinline__ void tap4u_issue(const char *__restrict__ base, unsig
     const f32x4 *p01 = reinterpret_cast<const f32x4 *>(base + (lane_off + ((unsigned)t.o01 << 7)));
     const f32x4 *p10 = reinterpret_cast<const f32x4 *>(base + (lane_off + ((unsigned)t.o10 << 7)));
     const f32x4 *p11 = reinterpret_cast<const f32x4 *>(base + (lane_off + ((unsigned)t.o11 << 7)));
-#if ENARF_DIAG_HALF_LOADS      // diagnosis builds only (wrong results): one 16-B load per lane and texel - what half-size texels would issue
-    r.a0 = p00[0]; r.a1 = r.a0; r.b0 = p01[0]; r.b1 = r.b0;
-    r.c0 = p10[0]; r.c1 = r.c0; r.d0 = p11[0]; r.d1 = r.d0;
-#else
     r.a0 = p00[0]; r.a1 = p00[1]; r.b0 = p01[0]; r.b1 = p01[1];
     r.c0 = p10[0]; r.c1 = p10[1]; r.d0 = p11[0]; r.d1 = p11[1];
-#endif
 }
 // Channel pairs as 2-vectors: each step is one v_pk_mul_f32 / v_pk_fma_f32 with the tap weight broadcast by op_sel
 // (16 VALU per plane). Written with vector types on purpose: from the scalar form the SLP vectoriser pairs TAPS instead
 // of channels for one of the three planes and pays ~50 moves and scalar adds per round to assemble the operands.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void tap4u_reduce(const TapRegs &r, const Taps &t, float s[8]) {
-#if ENARF_DIAG_SCALAR_REDUCE
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        s[c] = r.a0[c] * t.w00;
-        s[c] += r.b0[c] * t.w01;
-        s[c] += r.c0[c] * t.w10;
-        s[c] += r.d0[c] * t.w11;
-        s[4 + c] = r.a1[c] * t.w00;
-        s[4 + c] += r.b1[c] * t.w01;
-        s[4 + c] += r.c1[c] * t.w10;
-        s[4 + c] += r.d1[c] * t.w11;
-    }
-#else
     const f32x2 w00 = {t.w00, t.w00}, w01 = {t.w01, t.w01}, w10 = {t.w10, t.w10}, w11 = {t.w11, t.w11};
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -197,7 +111,6 @@ __device__ __forceinline__ void tap4u_reduce(const TapRegs &r, const Taps &t, fl
             s[4 * h + 2 * q + 1] = v[1];
         }
     }
-#endif
 }
 
 // acc[c] += weight * sum over planes xy, yz, zx of bilinear(feature plane, canonical)  (sampling.py:79-127)
@@ -670,7 +583,6 @@ __device__ __forceinline__ void query_tile(const QueryCtx &S, const int *cand_li
             if (dbg.weight && !v) dbg.weight[(size_t)k * dbg.N + dbg.i] = 0.125f;   // sigmoid(0)^3 (sampling.py)
         }
     }
-    TMR(S, 1);
     uint32_t b = mine | (uint32_t)quad_perm_i<0xB1>((int)mine);   // [1,0,3,2]
     b |= (uint32_t)quad_perm_i<0x4E>((int)b);                     // [2,3,0,1]
     bits = b;
@@ -684,104 +596,10 @@ __device__ __forceinline__ void query_tile(const QueryCtx &S, const int *cand_li
     const unsigned fplane_b = (unsigned)(mplane * kFeat * sizeof(float));        // bytes per feature plane
     const unsigned goff = (unsigned)g << 5;                                       // this lane's 32-B chunk
     uint32_t rem = b;
-#if ENARF_ROUND_PRIO
     // the gather rounds issue ahead of the other waves' MLP / sampling / compositing (+1.8 % at one frame; raising the
     // candidate tests too, or the MLP instead, gains less)
-    __builtin_amdgcn_s_setprio(ENARF_ROUND_PRIO);
-#endif
-#if ENARF_ROUND_SWPIPE && !ENARF_DIAG_TAPCHECK && ENARF_TIMERS != 2
-    // Software-pipelined rounds: the address generation of round r + 1 (next part of every point, bone transform, the
-    // lane's own plane taps: ~120 VALU instructions that need only LDS and registers) runs while the last 8 loads of
-    // round r (plane zx) are in flight - the point of the round with the fewest live registers - instead of in front
-    // of its own loads. Same arithmetic on the same operands as the plain loop below: bit-identical results.
-    uint64_t bal = __ballot(rem != 0);
-    bool act = false;
-    int k = 0;
-    Taps t;
-    auto round_addr = [&](bool &a_act, int &a_k, Taps &a_t) {
-        a_act = rem != 0;
-        a_k = a_act ? __builtin_ctz(rem) : 0;
-        rem &= rem - 1;
-        float F[13], Cn[12], lx, ly, lz, cx, cy, cz;
-        load_frames(S, a_k, F, Cn);
-        exact_local(F, px, py, pz, lx, ly, lz);
-        exact_canonical(Cn, F[12], lx, ly, lz, cx, cy, cz);
-        const float qx = (g == 1) ? cy : (g == 2) ? cz : cx;     // lane g owns plane g: xy, yz, zx (lane 3 repeats plane 0)
-        const float qy = (g == 1) ? cz : (g == 2) ? cx : cy;
-#if ENARF_DIAG_GENERAL_TAPS
-        a_t = make_taps(qx, qy, S.H, S.W);
-#else
-        a_t = make_taps_valid(qx, qy, S.H, S.W);
-#endif
-    };
-    if (bal != 0) round_addr(act, k, t);
-    while (bal != 0) {
-        const bool act_c = act;
-        const int k_c = k;
-        const uint64_t bal_c = bal;
-        float acc[8], w = 0.0f;
-        TapRegs r0, r1, r2;
-        Taps t1, t2;
-        if (act_c) {   // quad-uniform, so the quad broadcasts see all four lanes
-            const int gm = (g == 3) ? 0 : g;
-            const char *maskb = reinterpret_cast<const char *>(S.mask);
-            const unsigned moff = __umul24((unsigned)(3 * k_c + gm), (unsigned)mplane) << 2;
-#if ENARF_MASK_ROW_PAIRS
-            // the four part-probability taps as two 8-byte row pairs: the texture path charges a load instruction by the
-            // cache lines it touches (48 here: 16 quads x 3 planes), not by its width - two instructions instead of four
-            float m00, m01, m10, m11;
-            load_row_pair(maskb, moff, t.o00, t.xe, m00, m01);
-            load_row_pair(maskb, moff, t.o10, t.xe, m10, m11);
-#else
-            const float m00 = *reinterpret_cast<const float *>(maskb + (moff + ((unsigned)t.o00 << 2)));
-            const float m01 = *reinterpret_cast<const float *>(maskb + (moff + ((unsigned)t.o01 << 2)));
-            const float m10 = *reinterpret_cast<const float *>(maskb + (moff + ((unsigned)t.o10 << 2)));
-            const float m11 = *reinterpret_cast<const float *>(maskb + (moff + ((unsigned)t.o11 << 2)));
-#endif
-            const Taps t0 = quad_bcast_taps<0>(t);
-            t1 = quad_bcast_taps<1>(t);
-            tap4u_issue(featb, goff, t0, r0);
-            tap4u_issue(featb, goff + fplane_b, t1, r1);
-            __builtin_amdgcn_sched_barrier(0);
-            float macc = m00 * t.w00;   // part probability plane g (sampling.py:43-48, :62)
-            macc += m01 * t.w01;
-            macc += m10 * t.w10;
-            macc += m11 * t.w11;
-            if (S.clamp_mask) macc = fminf(fmaxf(macc, -2.0f), 5.0f);
-            const float sg = sigmoidf_(macc);
-            const float wp = (quad_bcast_f<0>(sg) * quad_bcast_f<1>(sg)) * quad_bcast_f<2>(sg);
-            w = (S.uniform_w > 0.0f) ? S.uniform_w : wp;
-            tap4u_reduce(r0, t0, acc);
-            pin8(acc);      // keep the reduction here: IR-level sinking would otherwise hold all 24 loads' registers
-            __builtin_amdgcn_sched_barrier(0);
-            t2 = quad_bcast_taps<2>(t);
-            tap4u_issue(featb, goff + 2u * fplane_b, t2, r2);
-            __builtin_amdgcn_sched_barrier(0);
-            float s1[8];
-            tap4u_reduce(r1, t1, s1);
-#pragma unroll
-            for (int c = 0; c < 8; ++c) acc[c] += s1[c];
-            pin8(acc);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        bal = __ballot(rem != 0);
-        if (bal != 0) round_addr(act, k, t);        // next round's addresses, while plane zx's loads are in flight
-        __builtin_amdgcn_sched_barrier(0);
-        if (act_c) {
-            float s2[8];
-            tap4u_reduce(r2, t2, s2);
-#pragma unroll
-            for (int c = 0; c < 8; ++c) acc[c] += s2[c];
-#pragma unroll
-            for (int c = 0; c < 8; ++c) feat[c] += acc[c] * w;
-            wmax = fmaxf(wmax, w);
-            if (DBG && dbg.weight && g == 0) dbg.weight[(size_t)k_c * dbg.N + dbg.i] = w;
-        }
-        n_pairs += (unsigned)(__popcll(bal_c) >> 2);
-        if (n_rounds) *n_rounds += 1;
-        TMR(S, 3);
-    }
-#else
+    constexpr int kRoundPrio = 2;
+    __builtin_amdgcn_s_setprio(kRoundPrio);
     while (true) {
         const uint64_t bal = __ballot(rem != 0);
         if (bal == 0) break;
@@ -795,57 +613,28 @@ __device__ __forceinline__ void query_tile(const QueryCtx &S, const int *cand_li
         // lane g owns plane g: xy, yz, zx (lane 3 repeats plane 0 and is ignored)
         const float qx = (g == 1) ? cy : (g == 2) ? cz : cx;
         const float qy = (g == 1) ? cz : (g == 2) ? cx : cy;
-        // the pair is valid: |canonical| < 1 strictly, the precondition of make_taps_valid (lanes without a pair compute
-        // garbage taps here and never use them: every load below sits behind `act`)
-#if ENARF_DIAG_TAPCHECK
+        // fully clamped taps, although the pair is valid (|canonical| < 1 strictly, the precondition of the lighter
+        // make_taps_valid, which measures the same: DESIGN.md 3.1). Lanes without a pair compute garbage taps here and
+        // never use them: every load below sits behind `act`
         const Taps t = make_taps(qx, qy, S.H, S.W);
-        if (act && S.diag) {
-            const Taps tv = make_taps_valid(qx, qy, S.H, S.W);
-            const int hw = S.H * S.W;
-            const bool oob = tv.o00 < 0 || tv.o00 >= hw || tv.o01 < 0 || tv.o01 >= hw || tv.o10 < 0 || tv.o10 >= hw || tv.o11 < 0 || tv.o11 >= hw;
-            const bool badk = k >= S.P;
-            const bool outside = !(fabsf(cx) < 1.0f && fabsf(cy) < 1.0f && fabsf(cz) < 1.0f);
-            if (oob || badk || outside) {
-                const unsigned long long kind = (oob ? 1ull : 0ull) | (badk ? 2ull : 0ull) | (outside ? 4ull : 0ull);
-                if (atomicAdd(&S.diag[5], 1ull) == 0ull) {
-                    S.diag[6] = (unsigned long long)S.diag_rid | ((unsigned long long)k << 32) | ((unsigned long long)lane << 40) | (kind << 48);
-                    S.diag[7] = (unsigned long long)__float_as_uint(qx) | ((unsigned long long)__float_as_uint(qy) << 32);
-                }
-            }
-        }
-#elif ENARF_DIAG_GENERAL_TAPS
-        const Taps t = make_taps(qx, qy, S.H, S.W);
-#else
-        const Taps t = make_taps_valid(qx, qy, S.H, S.W);
-#endif
         // Pipelined round: the 4 mask taps and the 16 feature loads of planes 0 and 1 are issued back to back; the
         // part probability is formed while they are in flight; plane 2's loads go out as soon as plane 0 is reduced.
         // Two exposed memory latencies per round (the serial form below has five: the compiler splits the mask taps
         // in two waits and each plane waits on its own).
-        TMR2(S, 7);
         if (act) {   // quad-uniform, so the quad broadcasts below see all four lanes
             const int gm = (g == 3) ? 0 : g;   // lane 3 repeats plane 0 (same addresses as lane 0: no extra traffic)
             const char *maskb = reinterpret_cast<const char *>(S.mask);
-            const unsigned moff = (ENARF_DIAG_NOMUL24 ? (unsigned)(3 * k + gm) * (unsigned)mplane : __umul24((unsigned)(3 * k + gm), (unsigned)mplane)) << 2;   // < 2^32 bytes, mplane < 2^24: check_common
-#if ENARF_MASK_ROW_PAIRS
+            const unsigned moff = __umul24((unsigned)(3 * k + gm), (unsigned)mplane) << 2;   // < 2^32 bytes, mplane < 2^24: check_common
             // the four part-probability taps as two 8-byte row pairs: the texture path charges a load instruction by the
             // cache lines it touches (48 here: 16 quads x 3 planes), not by its width - two instructions instead of four
             float m00, m01, m10, m11;
             load_row_pair(maskb, moff, t.o00, t.xe, m00, m01);
             load_row_pair(maskb, moff, t.o10, t.xe, m10, m11);
-#else
-            const float m00 = *reinterpret_cast<const float *>(maskb + (moff + ((unsigned)t.o00 << 2)));
-            const float m01 = *reinterpret_cast<const float *>(maskb + (moff + ((unsigned)t.o01 << 2)));
-            const float m10 = *reinterpret_cast<const float *>(maskb + (moff + ((unsigned)t.o10 << 2)));
-            const float m11 = *reinterpret_cast<const float *>(maskb + (moff + ((unsigned)t.o11 << 2)));
-#endif
             TapRegs r0, r1, r2;
             const Taps t0 = quad_bcast_taps<0>(t), t1 = quad_bcast_taps<1>(t);
             tap4u_issue(featb, goff, t0, r0);
             tap4u_issue(featb, goff + fplane_b, t1, r1);
             __builtin_amdgcn_sched_barrier(0);
-            TMR2(S, 0);
-            TMR2_WAIT(S, 1, 0x4F70);     // vmcnt(16)  (diagnostic build: meaningful with ENARF_MASK_ROW_PAIRS=0 only)
             float macc = m00 * t.w00;   // part probability plane g (sampling.py:43-48, :62)
             macc += m01 * t.w01;
             macc += m10 * t.w10;
@@ -855,8 +644,6 @@ __device__ __forceinline__ void query_tile(const QueryCtx &S, const int *cand_li
             const float wp = (quad_bcast_f<0>(sg) * quad_bcast_f<1>(sg)) * quad_bcast_f<2>(sg);
             const float w = (S.uniform_w > 0.0f) ? S.uniform_w : wp;
             float acc[8], s1[8], s2[8];
-            TMR2(S, 2);
-            TMR2_WAIT(S, 3, 0x0F78);     // vmcnt(8)
             tap4u_reduce(r0, t0, acc);
             pin8(acc);      // keep the reduction here: IR-level sinking would otherwise hold all 24 loads' registers
             __builtin_amdgcn_sched_barrier(0);
@@ -866,12 +653,7 @@ __device__ __forceinline__ void query_tile(const QueryCtx &S, const int *cand_li
             tap4u_reduce(r1, t1, s1);
 #pragma unroll
             for (int c = 0; c < 8; ++c) acc[c] += s1[c];
-#if ENARF_TIMERS == 2
-            pin8(acc);
-#endif
             __builtin_amdgcn_sched_barrier(0);
-            TMR2(S, 4);
-            TMR2_WAIT(S, 5, 0x0F70);     // vmcnt(0)
             tap4u_reduce(r2, t2, s2);
 #pragma unroll
             for (int c = 0; c < 8; ++c) acc[c] += s2[c];
@@ -879,22 +661,12 @@ __device__ __forceinline__ void query_tile(const QueryCtx &S, const int *cand_li
             for (int c = 0; c < 8; ++c) feat[c] += acc[c] * w;
             wmax = fmaxf(wmax, w);
             if (DBG && dbg.weight && g == 0) dbg.weight[(size_t)k * dbg.N + dbg.i] = w;
-#if ENARF_TIMERS == 2
-            pin8(feat);
-#endif
-            TMR2(S, 6);
         }
-        TMR(S, 3);
         n_pairs += (unsigned)(__popcll(bal) >> 2);
         if (n_rounds) *n_rounds += 1;
-        TMR(S, 3);
     }
-
-#endif
-#if ENARF_ROUND_PRIO
     __builtin_amdgcn_s_setprio(0);
-#endif
-    ran = (__ballot(b != 0) != 0) && !(ENARF_DIAG_ABLATE & 4);
+    ran = __ballot(b != 0) != 0;
     if (ran) {
         n_tiles += 1;
         float x[8];
@@ -905,7 +677,6 @@ __device__ __forceinline__ void query_tile(const QueryCtx &S, const int *cand_li
     } else {
         o = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     }
-    TMR(S, 4);
 }
 
 }  // namespace enarf

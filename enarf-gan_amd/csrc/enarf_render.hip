@@ -3,16 +3,6 @@
 #include "enarf_tasks.h"
 #include "enarf_host.h"
 
-#ifndef ENARF_S2_PRIO
-#define ENARF_S2_PRIO 3
-#endif
-#ifndef ENARF_RENDER_WAVES_PER_SIMD
-#define ENARF_RENDER_WAVES_PER_SIMD 3
-#endif
-
-#ifndef ENARF_BATCH_CLASSES
-#define ENARF_BATCH_CLASSES 4
-#endif
 namespace enarf {
 
 // =================================================================================================
@@ -225,9 +215,6 @@ __global__ __launch_bounds__(256) void query_kernel(const enarf_query_args a, in
     S.mask = a.mask_planes + (size_t)b * a.mask_batch_stride;
     S.H = a.H; S.W = a.W; S.P = a.P; S.mult_w = a.multiply_density_with_weight ? (a.uniform_part_weight ? 2 : 1) : 0;
     S.clamp_mask = a.clamp_mask; S.uniform_w = a.uniform_part_weight ? 1.0f / (float)a.P : 0.0f;
-#if ENARF_DIAG_TAPCHECK
-    S.diag = nullptr; S.diag_rid = 0;
-#endif
     // candidates of a 16-point tile: the parts whose bounding sphere contains at least one of its points (a free point
     // cloud - or the lattice of create_mesh, mostly empty space - has no ray set-up to cull for it); debug runs keep
     // every part, they export the canonical coordinates of all of them
@@ -551,9 +538,10 @@ __device__ __forceinline__ void ray_setup_block(const enarf_render_args &a, cons
     // part (batches only: a single image drops them) go to the band's list of missed rays
     constexpr int kFile = kClasses + 1;
     // more images than bands: a band holds several whole frames, and class-major order would walk each of them once per
-    // class (ENARF_BATCH_CLASSES: how many of the cost classes such batches use; measured: no difference)
+    // class (kBatchClasses: how many of the cost classes such batches use; measured: 1 or 2 make no difference)
+    constexpr int kBatchClasses = 4;
     const int cls = (cand == 0u) ? kClasses
-                    : (a.B > kQueues) ? min(ray_cost_class(cand), ENARF_BATCH_CLASSES - 1) : ray_cost_class(cand);
+                    : (a.B > kQueues) ? min(ray_cost_class(cand), kBatchClasses - 1) : ray_cost_class(cand);
     const bool file_it = live && g == 0;
     uint64_t bal[kFile];
 #pragma unroll
@@ -639,10 +627,15 @@ constexpr int SC_QUEUE = 1416;    // 2 ray ids (current / prefetched)
 constexpr int SC_BINS = 1480;     // importance samples of the ray [128] + 8 skip flags (written by the one wave that runs S2)
 static_assert(SC_QUEUE + kQueueLdsInts <= SC_BINS && SC_BINS + kMaxSamples + 8 <= kScratchFloats, "scratch overflow");
 
+// workgroups of render_kernel per CU = its waves per SIMD (168 VGPRs; measured: 4 spill 71 VGPRs, 0.250 vs 0.224 ms)
+constexpr int kRenderWavesPerSimd = 3;
+// priority of the one wave that runs S2 while the three others wait at the next barrier for it
+constexpr int kS2Prio = 3;
+
 // SPL = samples per lane in the lane = sample stages: 1 for Nc, Nf <= 64, 2 up to 128 (each wave then loops over two
 // 16-sample tiles per pass)
 template <int MODE, int SPL>
-__global__ __launch_bounds__(256, ENARF_RENDER_WAVES_PER_SIMD) void render_kernel(const enarf_render_args a) {
+__global__ __launch_bounds__(256, kRenderWavesPerSimd) void render_kernel(const enarf_render_args a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // Persistent workgroups: each marches one ray at a time, taken off the (band, cost class) lists the set-up pass
@@ -650,9 +643,6 @@ __global__ __launch_bounds__(256, ENARF_RENDER_WAVES_PER_SIMD) void render_kerne
     const int P = a.P, Nc = a.Nc, Nf = a.Nf, n = a.n;
     RayQueue rq;
 
-#if ENARF_TIMERS == 3   // workgroup start / end on the 100 MHz wall clock: how much of the launch is tail
-    const unsigned long long wg_t0 = __builtin_amdgcn_s_memrealtime();
-#endif
     QueryCtx S;
     float *scratch = lds + (lds_total_floats<MODE>(P) - kScratchFloats);
     int *l_q = reinterpret_cast<int *>(scratch + SC_QUEUE);
@@ -690,21 +680,8 @@ __global__ __launch_bounds__(256, ENARF_RENDER_WAVES_PER_SIMD) void render_kerne
     const int j4 = lane >> 2;                              // this lane's sample within the wave's tile
     const bool dbgq = (a.dbg_fine_density != nullptr);
 
-#if ENARF_TIMERS
-    for (int k = 0; k < 8; ++k) S.tmr[k] = 0;
-    S.tmr_t = __builtin_amdgcn_s_memtime();
-#endif
-#if ENARF_TIMERS == 3
-    unsigned long long ray_t0 = wg_t0, ray_max = 0;
-#endif
     while (cur >= 0) {
-#if ENARF_TIMERS == 3
-        { const unsigned long long now = __builtin_amdgcn_s_memrealtime(); if (now - ray_t0 > ray_max && n_rays) ray_max = now - ray_t0; ray_t0 = now; }
-#endif
         const uint32_t rid = (uint32_t)cur;
-#if ENARF_DIAG_TAPCHECK
-        S.diag = a.counters; S.diag_rid = rid;
-#endif
         // next entry (read after the S1 barrier): popped by the wave that has no coarse tile in this ray, when there is
         // one - the atomic's round trip then costs nothing
         const int spare_wave = (3 * SPL * 16 >= Nc) ? ((3 - (int)(rid & 3u)) & 3) : 0;
@@ -728,8 +705,6 @@ __global__ __launch_bounds__(256, ENARF_RENDER_WAVES_PER_SIMD) void render_kerne
         const int ncand = build_cand_list(l_cand, rec.cand, lane);
         const float sx = exact_mul(dmin, dx), sy = exact_mul(dmin, dy), sz = exact_mul(dmin, dz);
         const float ex = exact_mul(dmax, dx), ey = exact_mul(dmax, dy), ez = exact_mul(dmax, dz);
-        TMR(S, 0);
-        TMR4(S, 0);
 
         // ---- S1: coarse pass (rendering.py:119-131, :172) in FULL tiles of 16 bins: tile t of the ray goes to wave slot
         // t / SPL. With Nc = 48 that is three full tiles instead of four tiles of 12 - a quarter fewer gather rounds
@@ -761,7 +736,7 @@ __global__ __launch_bounds__(256, ENARF_RENDER_WAVES_PER_SIMD) void render_kerne
         float usort[SPL];
 #pragma unroll
         for (int s = 0; s < SPL; ++s) usort[s] = 0.0f;
-        if (wave == spare_wave && !a.bins && !(ENARF_DIAG_ABLATE & 8)) {
+        if (wave == spare_wave && !a.bins) {
             float esum[SPL];
             uint32_t r1_first = 0;
 #pragma unroll
@@ -776,11 +751,7 @@ __global__ __launch_bounds__(256, ENARF_RENDER_WAVES_PER_SIMD) void render_kerne
 #pragma unroll
             for (int s = 0; s < SPL; ++s) usort[s] = fminf(esum[s] / etot, 0.99999994f);
         }
-        TMR(S, 4);
-        TMR4(S, 7);
         __syncthreads();
-        TMR(S, 5);
-        TMR4(S, 6);
         const int next_ray = rq.get(qslot ^ 1);
         qslot ^= 1;
 
@@ -790,9 +761,7 @@ __global__ __launch_bounds__(256, ENARF_RENDER_WAVES_PER_SIMD) void render_kerne
         float *l_bins = scratch + SC_BINS;
         int *l_skip = reinterpret_cast<int *>(scratch + SC_BINS + kMaxSamples);
         if (wave == spare_wave) {
-#if ENARF_S2_PRIO
-            __builtin_amdgcn_s_setprio(ENARF_S2_PRIO);     // three waves wait at the next barrier for this one
-#endif
+            __builtin_amdgcn_s_setprio(kS2Prio);
             float bin[SPL];
             bool skip_tile[4 * SPL];
 
@@ -823,11 +792,7 @@ __global__ __launch_bounds__(256, ENARF_RENDER_WAVES_PER_SIMD) void render_kerne
                 if (e >= Nc - 1) wr[s] = 0.0f;
                 ws[s] = (e < Nc) ? (fmaxf(wl[s], wgt[s]) + fmaxf(wgt[s], wr[s])) / 2.0f + 0.01f : 0.0f;
             }
-            TMR4(S, 1);
-            if (ENARF_DIAG_ABLATE & 8) {
-#pragma unroll
-                for (int s = 0; s < SPL; ++s) bin[s] = (float)(64 * s + lane) / (float)Nf;
-            } else if (a.bins) {
+            if (a.bins) {
 #pragma unroll
                 for (int s = 0; s < SPL; ++s) bin[s] = a.bins[((size_t)b * n + ray) * Nf + min(64 * s + lane, Nf - 1)];
             } else {
@@ -875,15 +840,9 @@ __global__ __launch_bounds__(256, ENARF_RENDER_WAVES_PER_SIMD) void render_kerne
                 }
                 if (lane == 0) l_skip[t] = skip_tile[t] ? 1 : 0;
             }
-#if ENARF_S2_PRIO
             __builtin_amdgcn_s_setprio(0);
-#endif
         }
-        TMR(S, 6);
-        TMR4(S, 2);
         __syncthreads();
-        TMR(S, 5);
-        TMR4(S, 6);
 
         // ---- S3: fine pass, in full tiles of 16 samples like the coarse pass (tile T on wave slot T / SPL; Nf = 48 or 32
         // leave one or two waves without a tile); the last sample only closes the last interval and is never queried
@@ -911,11 +870,7 @@ __global__ __launch_bounds__(256, ENARF_RENDER_WAVES_PER_SIMD) void render_kerne
                 if (skip && lane == 0) n_skipped += 1;
             }
         }
-        TMR(S, 4);
-        TMR4(S, 7);
         __syncthreads();
-        TMR(S, 5);
-        TMR4(S, 6);
 
         // ---- S4 (one wave, element e = 64 s + lane): compositing (rendering.py:307-335). It runs while the other waves are
         // already in the next ray's coarse pass - on the wave that has no coarse tile there, when there is one.
@@ -942,7 +897,6 @@ __global__ __launch_bounds__(256, ENARF_RENDER_WAVES_PER_SIMD) void render_kerne
                     }
                 }
             }
-            TMR4(S, 3);
             wv_next<SPL>(fdepth, dnext, lane);
 #pragma unroll
             for (int s = 0; s < SPL; ++s) {
@@ -959,7 +913,6 @@ __global__ __launch_bounds__(256, ENARF_RENDER_WAVES_PER_SIMD) void render_kerne
                 vr[s] = wgt[s] * cr[s]; vg[s] = wgt[s] * cg[s]; vb[s] = wgt[s] * cb[s];
                 vd[s] = seg ? (wgt[s] * 1.0f) / fdepth[s] : 0.0f;
             }
-            TMR4(S, 4);
             const float o_r = wv_sum<SPL>(vr), o_g = wv_sum<SPL>(vg), o_b = wv_sum<SPL>(vb);
             const float o_m = wv_sum<SPL>(wgt), o_d = wv_sum<SPL>(vd);
             if (lane == 0) {
@@ -976,31 +929,10 @@ __global__ __launch_bounds__(256, ENARF_RENDER_WAVES_PER_SIMD) void render_kerne
                 if (a.fine_depth && e < Nf) a.fine_depth[((size_t)b * n + ray) * Nf + e] = fdepth[s];
             }
         }
-        TMR(S, 7);
-        TMR2(S, 7);
-        TMR4(S, 5);
         // no barrier needed here: coarse arrays are rewritten in S1' (after this ray's S3 barrier, which follows every
         // wave's S2 reads), fine arrays in S3' (after the S1' barrier, which wave 0 reaches only after this S4).
         cur = next_ray;
     }
-#if ENARF_TIMERS == 3
-    if (a.counters && tid == 0) {
-        const unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
-        atomicMin(&a.counters[0], wg_t0);
-        atomicMax(&a.counters[1], t1);
-        atomicAdd(&a.counters[2], t1 - wg_t0);
-        atomicAdd(&a.counters[3], 1ull);
-        atomicMax(&a.counters[4], wg_t0);
-        atomicMin(&a.counters[5], t1);
-        atomicAdd(&a.counters[6], t1 - ray_t0);      // duration of this workgroup's last ray
-        atomicMax(&a.counters[7], ray_max);          // longest ray of the launch
-    }
-    return;
-#elif ENARF_TIMERS
-    if (a.counters && lane == 0)
-        for (int k = 0; k < 8; ++k) atomicAdd(&a.counters[k], S.tmr[k]);
-    return;
-#endif
     if (a.counters && lane == 0) {
         atomicAdd(&a.counters[0], (unsigned long long)n_pairs);
         atomicAdd(&a.counters[1], (unsigned long long)n_tiles);
@@ -1143,28 +1075,19 @@ int device_cus() {
 // Two march kernels share every stage (enarf_march.h, enarf_query.h, enarf_tasks.h) and produce the same bits:
 //   render_kernel   one workgroup (4 waves) marches one ray at a time, 3 workgroups per CU, three barriers per ray;
 //   march_kernel    one workgroup (12 waves) per CU, several rays in flight, 16-sample tiles claimed as tasks.
-// ENARF_TASK_MARCH: 0 / 1 force one of them (A/B builds); 2 (product) picks by shape, from measurements on MI355X
-// (DESIGN.md 3.1): the task march wins where a pass has more tiles than a 4-wave workgroup has waves (Nc or Nf > 64:
-// 0.31 vs 0.36 ms at 128^2, 72 + 96), ties at 48 + 64 (0.225 vs 0.225) and loses on batches, where every change of
-// image drains its pipeline (8 frames: 2.60 vs 1.79 ms).
-#ifndef ENARF_TASK_MARCH
-#define ENARF_TASK_MARCH 2
-#endif
-#ifndef ENARF_TASK_WAVES
-#define ENARF_TASK_WAVES 12
-#endif
-#ifndef ENARF_TASK_SLOTS
-#define ENARF_TASK_SLOTS 6
-#endif
+// enarf_render_args.march picks one; ENARF_MARCH_AUTO picks by shape, from measurements on MI355X: the
+// task march wins where a pass has more tiles than a 4-wave workgroup has waves (Nc or Nf > 64: 0.31 vs 0.36 ms at 128^2,
+// 72 + 96), ties at 48 + 64 (0.225 vs 0.225) and loses on batches, where every change of image drains its pipeline
+// (8 frames: 2.60 vs 1.79 ms).
 
 template <int MODE, int SPL>
 static int launch_task_march(const enarf_render_args &a, hipStream_t st, bool with_setup) {
-    constexpr int NW = ENARF_TASK_WAVES;
+    constexpr int NW = 12;               // waves per workgroup (measured: 16, at 128 VGPRs, spill: 0.26-0.34 vs 0.225 ms)
     const int num_cus = device_cus();
     if (num_cus <= 0) return host::fail((int)hipGetLastError(), "enarf_render_fwd: cannot query the device");
     const long long total = (long long)a.B * a.n;
     // rays in flight per workgroup: enough tiles for every wave (3-4 per ray and stage), never more than there are rays
-    int nslots = ENARF_TASK_SLOTS;
+    int nslots = 6;                      // measured: 4 slots 0.2381 ms, 5 0.2262, 6 0.2253, 7 0.2284, 8 0.2326
     long long wgs = num_cus;
     if (wgs * nslots > total) {          // few rays: spread them over the CUs first
         nslots = (int)((total + wgs - 1) / wgs);
@@ -1187,18 +1110,14 @@ static int launch_task_march(const enarf_render_args &a, hipStream_t st, bool wi
 
 template <int MODE, int SPL>
 static int launch_render(const enarf_render_args &a, hipStream_t st, bool with_setup) {
-#if ENARF_TASK_MARCH == 1
-    return launch_task_march<MODE, SPL>(a, st, with_setup);
-#elif ENARF_TASK_MARCH == 2
     if (a.march == ENARF_MARCH_TASK || (a.march == ENARF_MARCH_AUTO && SPL == 2 && a.B == 1))
         return launch_task_march<MODE, SPL>(a, st, with_setup);
-#endif
     // persistent grid: as many workgroups as stay resident (3 per CU at <= 168 VGPRs and ~37 KB LDS), never more
     // than there are rays
     const int num_cus = device_cus();
     if (num_cus <= 0) return host::fail((int)hipGetLastError(), "enarf_render_fwd: cannot query the device");
     const long long total = (long long)a.B * a.n;
-    long long wgs = (long long)num_cus * ENARF_RENDER_WAVES_PER_SIMD;
+    long long wgs = (long long)num_cus * kRenderWavesPerSimd;
     if (wgs > total) wgs = total;
     const size_t lds = (size_t)lds_total_floats<MODE>(a.P) * 4;
     if (with_setup)

@@ -14,16 +14,6 @@
 #include "enarf_march.h"
 #include "enarf_host.h"
 
-#ifndef ENARF_BWD_PARITY_WALK          // 0 = round 2's walkers by tap slot (A/B)
-#define ENARF_BWD_PARITY_WALK 1
-#endif
-#ifndef ENARF_BWD_NS_FIXED
-#define ENARF_BWD_NS_FIXED 0
-#endif
-#ifndef ENARF_BWD_ABLATE
-#define ENARF_BWD_ABLATE 0      // diagnosis builds only: 1 no feature atomics, 2 no mask atomics, 4 no scatter pass, 8 no row export
-#endif
-
 namespace enarf {
 
 constexpr int kBwdWavesPerSimd = 2;
@@ -67,7 +57,7 @@ __device__ __forceinline__ void scatter_tap2(float *__restrict__ gpl, float *til
     // x0 and x0 + 1 - their offsets always differ in parity - so every occurrence of a texel lands with the same walker, and a
     // sample's x0 + 1 meeting the next sample's x0 (the ray advanced by one texel) is one run instead of two atomics:
     // 686 -> 613 B of feature lines per valid pair (tests/analysis/atomic_merge.py), what the 6x6 LDS window bought at 2-3x the time.
-    if (ENARF_BWD_PARITY_WALK && (offA & 1)) {
+    if (offA & 1) {
         const int to = offA; offA = offB; offB = to;
         const float tc = cfA; cfA = cfB; cfB = tc;
     }
@@ -94,12 +84,12 @@ __device__ __forceinline__ void scatter_tap2(float *__restrict__ gpl, float *til
             if (o == run_o) {
                 run_v += v;
             } else {
-                if (run_o >= 0 && !(ENARF_BWD_ABLATE & 1)) { atomicAdd(gpl + (size_t)run_o * kFeat + ch, run_v); n_lines += 1; }
+                if (run_o >= 0) { atomicAdd(gpl + (size_t)run_o * kFeat + ch, run_v); n_lines += 1; }
                 run_o = o;
                 run_v = v;
             }
         }
-        if (run_o >= 0 && !(ENARF_BWD_ABLATE & 1)) { atomicAdd(gpl + (size_t)run_o * kFeat + ch, run_v); n_lines += 1; }
+        if (run_o >= 0) { atomicAdd(gpl + (size_t)run_o * kFeat + ch, run_v); n_lines += 1; }
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -112,7 +102,7 @@ __device__ __forceinline__ void scatter_plane(float *__restrict__ gpl, float *ti
     // has ONE walker that sees every occurrence of it, and along a ray - which crosses texels monotonically - those are
     // consecutive samples: run merging alone removes every duplicate of the tile (tests/analysis/atomic_merge.py: "tile
     // uniq"), with no LDS table.
-    const bool up = !ENARF_BWD_PARITY_WALK || t.yp == 0;      // the upper row (y0) is the even one
+    const bool up = t.yp == 0;      // the upper row (y0) is the even one
     scatter_tap2(gpl, tile, up ? t.o00 : t.o10, (up ? t.w00 : t.w10) * wk, up ? t.o01 : t.o11, (up ? t.w01 : t.w11) * wk, on, dxg, lane, n_lines);
     scatter_tap2(gpl, tile, up ? t.o10 : t.o00, (up ? t.w10 : t.w00) * wk, up ? t.o11 : t.o01, (up ? t.w11 : t.w01) * wk, on, dxg, lane, n_lines);
 }
@@ -143,39 +133,6 @@ __device__ __forceinline__ void mask_tap_add(float *__restrict__ gmask, bool on,
     }
     const bool tail = dpp_i(-1, key, 2) != key;                   // the next quad starts another run (or the row ends)
     if (on && tail) { atomicAdd(gmask + elem, acc); n_adds += 1; }
-}
-
-// A/B (ENARF_BWD_MASK_ROWMAJOR=1): the same adds with the wave re-laid as lane = 32 row + 2 sample + x-tap, so that all
-// taps of one texel row sit in consecutive lanes (one permute each for the element and the value), runs of equal elements
-// merged along the samples (lanes 2 apart, rows of 8 samples) - does the memory side then see one request per touched
-// 64-byte segment instead of one per sample and row?
-#ifndef ENARF_BWD_F4_ROUNDS            // A/B: rounds of the scatter pass whose loads are all issued before any of their atomics.
-#define ENARF_BWD_F4_ROUNDS 1          // 1 = loads and adds alternate round by round. Measured at C1: 1 -> 1.628 ms, 4 -> 1.660, 8 -> 1.653
-#endif
-#ifndef ENARF_BWD_MASK_ROWMAJOR
-#define ENARF_BWD_MASK_ROWMAJOR 0
-#endif
-__device__ __forceinline__ void mask_tap_add_rowmajor(float *__restrict__ gmask, bool on, int elem, float v, int lane, unsigned &n_adds) {
-    // source lane (sample q, tap t = 2 row + x) = 4 q + t  ->  lane 32 row + 2 q + x
-    const int src = 4 * ((lane >> 1) & 15) + 2 * (lane >> 5) + (lane & 1);
-    const int key_own = on ? elem : -2 - lane;
-    const int key = __builtin_amdgcn_ds_bpermute(src << 2, key_own);
-    float acc = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src << 2, __builtin_bit_cast(int, on ? v : 0.0f)));
-    const bool live = key >= 0;
-    auto shr = [](int old, int x, int sel) {
-        return sel == 0 ? __builtin_amdgcn_update_dpp(old, x, 0x112, 0xF, 0xF, false)       // row_shr:2
-             : sel == 1 ? __builtin_amdgcn_update_dpp(old, x, 0x114, 0xF, 0xF, false)       // row_shr:4
-                        : __builtin_amdgcn_update_dpp(old, x, 0x118, 0xF, 0xF, false);      // row_shr:8
-    };
-    int head = (shr(-1, key, 0) != key) ? 1 : 0;
-#pragma unroll
-    for (int sel = 0; sel < 3; ++sel) {
-        const float pv = __builtin_bit_cast(float, shr(0, __builtin_bit_cast(int, acc), sel));
-        const int ph = shr(1, head, sel);
-        if (!head) { acc += pv; head |= ph; }
-    }
-    const bool tail = __builtin_amdgcn_update_dpp(-1, key, 0x102, 0xF, 0xF, false) != key;      // row_shl:2: the next sample starts another run
-    if (live && tail) { atomicAdd(gmask + key, acc); n_adds += 1; }
 }
 
 // what the per-tile stages of the backward need besides the query context (shared by the ray and the point kernels)
@@ -218,7 +175,7 @@ __device__ __forceinline__ void bwd_gather_tile(const QueryCtx &S, const BwdTile
         bits |= (uint32_t)quad_perm_i<0x4E>((int)bits);
 #pragma unroll
         for (int c = 0; c < 8; ++c) feat[c] = 0.0f;
-        uint32_t rem = (ENARF_BWD_ABLATE & 4) ? 0u : bits;
+        uint32_t rem = bits;
         while (true) {
             const uint64_t bal = __ballot(rem != 0);
             if (bal == 0) break;
@@ -275,12 +232,10 @@ __device__ __forceinline__ void bwd_backward_tile(const QueryCtx &S, const BwdTi
     if (lane == 0) blk = atomicAdd(T.row_blocks + b, 1u);
     blk = (unsigned int)__builtin_amdgcn_readfirstlane((int)blk);
     const size_t row = (size_t)b * T.rows_per_image + (size_t)blk * 16 + mj;
-    if (!(ENARF_BWD_ABLATE & 8)) {
-        f32x4 *rx = reinterpret_cast<f32x4 *>(T.rows_x + row * 32 + 8 * mg);
-        rx[0] = f32x4{x[0], x[1], x[2], x[3]};
-        rx[1] = f32x4{x[4], x[5], x[6], x[7]};
-        T.rows_dz3[row * 4 + mg] = dz3v;
-    }
+    f32x4 *rx = reinterpret_cast<f32x4 *>(T.rows_x + row * 32 + 8 * mg);
+    rx[0] = f32x4{x[0], x[1], x[2], x[3]};
+    rx[1] = f32x4{x[4], x[5], x[6], x[7]};
+    T.rows_dz3[row * 4 + mg] = dz3v;
     C.tiles += 1;
     // d feature back in the gather layout
     float dxg[8];
@@ -295,8 +250,9 @@ __device__ __forceinline__ void bwd_backward_tile(const QueryCtx &S, const BwdTi
     // and no-return atomics share vmcnt, so a wait for a load result while atomics are outstanding is s_waitcnt vmcnt(0) and
     // drains every atomic the wave has in flight; alternating round by round that is one drain per round, in chunks one per
     // chunk. Measured (profiles/r03_bwd_lds_merge_ab.log): no gain - 1.628 ms (1), 1.660 (4), 1.653 (8) at C1: the waves are
-    // not waiting on those drains. The product keeps chunks of 1.
-    constexpr int kF4Rounds = ENARF_BWD_F4_ROUNDS;
+    // not waiting on those drains. The product keeps chunks of 1, in this chunked form: the same round written as a plain
+    // loop is allocated differently and spills more.
+    constexpr int kF4Rounds = 1;
     auto round_taps = [&](int k) {      // this lane's own-plane taps of part k at the sample (lane 3 repeats plane 0)
         float F[13], Cn[12], lx, ly, lz, cx, cy, cz;
         load_frames(S, k, F, Cn);
@@ -306,7 +262,7 @@ __device__ __forceinline__ void bwd_backward_tile(const QueryCtx &S, const BwdTi
         const float qy = (g4 == 1) ? cz : (g4 == 2) ? cx : cy;
         return make_taps(qx, qy, T.H, T.W);
     };
-    uint32_t rem = (ENARF_BWD_ABLATE & 4) ? 0u : bits;
+    uint32_t rem = bits;
     __builtin_amdgcn_s_setprio(2);          // memory rounds ahead of the other waves' MFMA phases (as in the forward)
     while (__ballot(rem != 0) != 0) {
         float wk_r[kF4Rounds], gm_r[kF4Rounds];
@@ -367,7 +323,7 @@ __device__ __forceinline__ void bwd_backward_tile(const QueryCtx &S, const BwdTi
                     // paid for (round 2 issued one instruction per tap slot with lane = (quad, plane): every add its own request -
                     // 8.3 M of the 20.4 M requests of a C1 backward, profiles/r03_bwd_a_pmc_summary.txt). Uniform weights
                     // (no_selector): no plane gradient
-                    const bool mon = act && !(ENARF_BWD_ABLATE & 2) && !(S.uniform_w > 0.0f);
+                    const bool mon = act && !(S.uniform_w > 0.0f);
 #define ENARF_MASK_PLANE(PL)                                                                                                   \
                     {   /* all broadcasts run with the whole quad enabled (a DPP read of a disabled lane returns nothing) */      \
                         const int o0 = quad_bcast_i<PL>(t.o00), o1 = quad_bcast_i<PL>(t.o01), o2 = quad_bcast_i<PL>(t.o10), o3 = quad_bcast_i<PL>(t.o11); \
@@ -376,16 +332,13 @@ __device__ __forceinline__ void bwd_backward_tile(const QueryCtx &S, const BwdTi
                         /* lane role = (row parity g4 >> 1, offset parity g4 & 1): the footprint texel with those parities - every  \
                            occurrence of a texel meets the same lane role, so runs along the samples merge ALL its duplicates */      \
                         const int ypb = quad_bcast_i<PL>(t.yp);                                                                \
-                        const bool r1 = ENARF_BWD_PARITY_WALK ? (ypb != (g4 >> 1)) : (g4 >> 1) != 0;                            \
+                        const bool r1 = ypb != (g4 >> 1);                                                                      \
                         const int oA = r1 ? o2 : o0, oB = r1 ? o3 : o1;                                                        \
                         const float wA = r1 ? w2 : w0, wB = r1 ? w3 : w1;                                                      \
-                        const bool tb = ENARF_BWD_PARITY_WALK ? ((oA & 1) != (g4 & 1)) : (g4 & 1) != 0;                         \
+                        const bool tb = (oA & 1) != (g4 & 1);                                                                  \
                         const int o = tb ? oB : oA;                                                                            \
                         const float w = tb ? wB : wA;                                                                          \
-                        if (ENARF_BWD_MASK_ROWMAJOR)                                                                           \
-                            mask_tap_add_rowmajor(T.gmask, mon && w != 0.0f, (3 * k + PL) * (int)T.mplane + o, w * gp, lane, C.mask_adds); \
-                        else                                                                                                   \
-                            mask_tap_add(T.gmask, mon && w != 0.0f, (3 * k + PL) * (int)T.mplane + o, w * gp, lane, C.mask_adds); \
+                        mask_tap_add(T.gmask, mon && w != 0.0f, (3 * k + PL) * (int)T.mplane + o, w * gp, lane, C.mask_adds);  \
                     }
                     ENARF_MASK_PLANE(0)
                     ENARF_MASK_PLANE(1)
@@ -434,11 +387,7 @@ __global__ __launch_bounds__(256, kBwdWavesPerSimd) void render_bwd_kernel(const
     // LDS: [fp32 weights PK_B1][bias 144][transposed PKT_FLOATS][parts][canon][scratch]
     float *l_w = lds, *l_bias = l_w + PK_B1, *l_wt = l_bias + 144, *l_parts = l_wt + PKT_FLOATS;
     float *l_canon = l_parts + P * kLdsPartStride, *scratch = l_canon + P * kLdsCanonStride;
-#if ENARF_BWD_NS_FIXED                               // A/B only: round 2's fixed 128-sample layout (one workgroup per CU)
-    constexpr int NS = kBwdMaxSamples;
-#else
     constexpr int NS = 64 * SPL;                    // stride of the per-sample LDS arrays
-#endif
     int *l_q = reinterpret_cast<int *>(scratch + sb_queue(NS));
     rq.init(a.workspace, 0, a.B, n, l_q, tid);      // the backward's own set-up launch runs with epoch 0
     if (tid == 0) rq.pop(0);
@@ -1056,7 +1005,7 @@ static int launch_bwd_group(const enarf_render_bwd_args &a, hipStream_t st) {
     const long long total = (long long)a.B * a.n;
     if (wgs > total) wgs = total;
     if (a.Nf > 64) hipLaunchKernelGGL(render_bwd_kernel<2>, dim3((unsigned)wgs), dim3(256), (size_t)bwd_lds_floats(a.P, 128) * 4, st, a);
-    else hipLaunchKernelGGL(render_bwd_kernel<1>, dim3((unsigned)wgs), dim3(256), (size_t)bwd_lds_floats(a.P, ENARF_BWD_NS_FIXED ? 128 : 64) * 4, st, a);
+    else hipLaunchKernelGGL(render_bwd_kernel<1>, dim3((unsigned)wgs), dim3(256), (size_t)bwd_lds_floats(a.P, 64) * 4, st, a);
     return host::check_launch("enarf_render_bwd");
 }
 

@@ -255,10 +255,7 @@ __device__ __noinline__ void ray_sample_stage(RenderArgsK a, const float *l_btab
         if (e >= Nc - 1) wr[s] = 0.0f;
         ws[s] = (e < Nc) ? (fmaxf(wl[s], wgt[s]) + fmaxf(wgt[s], wr[s])) / 2.0f + 0.01f : 0.0f;
     }
-    if (ENARF_DIAG_ABLATE & 8) {
-#pragma unroll
-        for (int s = 0; s < SPL; ++s) bin[s] = (float)(64 * s + lane) / (float)Nf;
-    } else if (a->bins) {
+    if (a->bins) {
 #pragma unroll
         for (int s = 0; s < SPL; ++s) bin[s] = a->bins[((size_t)b * n + ray) * Nf + min(64 * s + lane, Nf - 1)];
     } else {
@@ -367,9 +364,6 @@ __device__ __forceinline__ void ray_tile_task(const enarf_render_args &a, const 
     const int b = (int)(rid / (uint32_t)n);
     S.feat = a.feat_cl + (size_t)b * a.feat_batch_stride;
     S.mask = a.mask_planes + (size_t)b * a.mask_batch_stride;
-#if ENARF_DIAG_TAPCHECK
-    S.diag = a.counters; S.diag_rid = rid;
-#endif
     const int ncand = (int)sw[SL_NCAND];
     const int *l_cand = reinterpret_cast<const int *>(sw + SL_CAND);
     const float dmin = rec.dmin, dmax = rec.dmax;
@@ -447,10 +441,7 @@ __device__ __forceinline__ void missed_ray_short_cut(RenderArgsK a, uint32_t rid
     }
 }
 
-#ifndef ENARF_MISSED_CHUNK
-#define ENARF_MISSED_CHUNK 32
-#endif
-constexpr int kMissedChunk = ENARF_MISSED_CHUNK;
+constexpr int kMissedChunk = 32;
 template <int SPL>
 __device__ __forceinline__ unsigned march_missed_rays(RenderArgsK ak, const float *l_btab, unsigned *scratch, int mult_w, int lane) {
     const int B = ak->B, n = ak->n, Nc = ak->Nc;
@@ -461,8 +452,8 @@ __device__ __forceinline__ unsigned march_missed_rays(RenderArgsK ak, const floa
     if (wsh[2] == 0u) return 0u;                 // no such ray in this launch (always so for a single image): one load
     const long long band = ws_band_size(B, n);
     const int home = xcc_id() & (kQueues - 1);
-    // debug runs (taps wanted) and the diagnostic fixed-grid build take the two general stages on a zeroed scratch slot
-    const bool general = ak->dbg_fine_density || ak->dbg_coarse_density || (ENARF_DIAG_ABLATE & 8);
+    // debug runs (taps wanted) take the two general stages on a zeroed scratch slot
+    const bool general = ak->dbg_fine_density || ak->dbg_coarse_density;
     float cdf[SPL];
 #pragma unroll
     for (int s = 0; s < SPL; ++s) cdf[s] = (64 * s + lane < Nc) ? (0.0f + 0.0f) / 2.0f + 0.01f : 0.0f;
@@ -654,9 +645,6 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void march_kernel(const enarf_rend
     S.feat = a.feat_cl; S.mask = a.mask_planes;
     S.H = a.H; S.W = a.W; S.P = P; S.mult_w = a.multiply_density_with_weight ? (a.uniform_part_weight ? 2 : 1) : 0;
     S.clamp_mask = a.clamp_mask; S.uniform_w = a.uniform_part_weight ? 1.0f / (float)P : 0.0f;
-#if ENARF_DIAG_TAPCHECK
-    S.diag = nullptr; S.diag_rid = 0;
-#endif
     MarchCtx M;
     M.slots = reinterpret_cast<unsigned *>(after);
     M.sh = M.slots + nslots * kSlotWords;
@@ -711,15 +699,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void march_kernel(const enarf_rend
     }
     __syncthreads();
     if (wave == 0) publish_ray(M, M.slots, lane);   // slot 0 holds the first ray (and one of the initial tokens)
-#if ENARF_TIMERS == 5   // diagnostic build: per-wave cycles in 0 tiles, 1 S2, 2 S4, 3 refill after S4 (+ start-up), 4 idle, 5 scan + claim, 6 pop-ahead
-    unsigned long long tm[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t_last = __builtin_amdgcn_s_memtime();
-#define TK(k) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); tm[k] += now_ - t_last; t_last = now_; } while (0)
-#else
-#define TK(k) do { } while (0)
-#endif
     for (int s = wave; s < nslots; s += NW)
         if (s != 0) C.rays += refill_slot<MODE>(ak, M, tq, lds, s, lane);
-    TK(3);
 
     volatile unsigned *vsl = M.slots;
     volatile unsigned *vsh = M.sh;
@@ -736,15 +717,13 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void march_kernel(const enarf_rend
             const int s = hi ? __builtin_ctzll(hi) : __builtin_ctzll(set);
             const unsigned old = (unsigned)__builtin_amdgcn_readlane((int)c, s);
             unsigned *sw = M.slots + s * kSlotWords;
-            if (wave_lds_cas(&sw[SL_CTL], old, old + 1u, lane) != old) { TK(5); continue; }      // taken or recycled meanwhile: look again
+            if (wave_lds_cas(&sw[SL_CTL], old, old + 1u, lane) != old) continue;      // taken or recycled meanwhile: look again
             lds_acquire();
             const bool fine = ctl_stage(old) == ST_FINE;
             idle = 0u;
-            TK(5);
             ray_tile_task<MODE>(a, M, S, sw, fine, (int)ctl_next(old), lane, C);
             lds_release();
             const unsigned d = wave_lds_add(&sw[SL_DONE], 1u, lane);
-            TK(0);
             if (d + 1u == ctl_tiles(old)) {          // this wave completed the stage: the serial follow-up is its job
                 lds_acquire();
                 if (!fine) {
@@ -756,18 +735,14 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void march_kernel(const enarf_rend
                     if (lane == 0)
                         __hip_atomic_store(&sw[SL_CTL], pack_ctl(ctl_gen(old), ST_FINE, (unsigned)M.nft, 0u), __ATOMIC_RELAXED,
                                            __HIP_MEMORY_SCOPE_WORKGROUP);
-                    TK(1);
                     __builtin_amdgcn_s_setprio(1);
                     C.rays += prefetch_next_ray(tq, sw, lane);
                     __builtin_amdgcn_s_setprio(0);
-                    TK(6);
                 } else {
                     __builtin_amdgcn_s_setprio(3);   // the slot is empty until this chain has published its next ray
                     ray_composite_stage<SPL>(ak, sw, S.mult_w, lane);
-                    TK(2);
                     C.rays += refill_slot<MODE>(ak, M, tq, lds, s, lane);       // the slot keeps its token across the pop
                     __builtin_amdgcn_s_setprio(0);
-                    TK(3);
                 }
             }
             continue;
@@ -784,13 +759,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void march_kernel(const enarf_rend
             break;
         }
         __builtin_amdgcn_s_sleep(4);
-        TK(4);
     }
-#if ENARF_TIMERS == 5
-    if (a.counters && lane == 0)
-        for (int k = 0; k < 8; ++k) atomicAdd(&a.counters[k], tm[k]);
-    return;
-#endif
     if (a.counters && lane == 0) {
         atomicAdd(&a.counters[0], (unsigned long long)C.pairs);
         atomicAdd(&a.counters[1], (unsigned long long)C.tiles);

@@ -8,8 +8,8 @@ rc=0; python -m pytest tests -m gpu -q > $O/pytest_full.log 2>&1 || rc=$?
 grep -v amdgpu.ids $O/pytest_full.log | tail -6 | tee $O/pytest.log
 if [ $rc -gt 1 ]; then echo "pytest rc=$rc: stopping"; exit $rc; fi
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | grep -v amdgpu.ids | tail -2
-# determinism of the product library on the ray subset of profiles/r02_mfma_hazard_fixed.log's last two runs
-NRAYS=3000 REPS=4 MODES=f16x3,bf16x3 python tools/tapcheck.py 2>&1 | grep -v amdgpu.ids | tee $O/determinism_nrays3000.log
+# determinism of the product library: both march kernels, three times each, on one case
+python tests/analysis/diag_march_eq.py 2>&1 | grep -v amdgpu.ids | tee $O/determinism.log
 bash tools/gpu_multi_rehearsal.sh
 python bench.py --steps 200 2>/dev/null | tee $O/bench_default.json | python tools/exline.py default
 python bench.py --steps 20 --warmup 5 2>/dev/null | tee $O/bench_driver_like.json | python tools/exline.py driver-like-20-steps

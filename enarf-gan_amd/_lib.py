@@ -177,6 +177,7 @@ SIGNATURES = {
     "enarf_upfirdn2d_out_size": (C.c_int, [C.c_int] * 6),
     "enarf_upfirdn2d": (C.c_int, [_f32p, _f32p, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_int,
                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "enarf_upfirdn2d_plan": (C.c_int, [C.c_longlong] + [C.c_int] * 11 + [C.POINTER(C.c_int)]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -264,9 +264,20 @@ extern "C" int enarf_upfirdn2d_out_size(int in_size, int taps, int up, int down,
     return (int)(padded / down + 1);
 }
 
-extern "C" int enarf_upfirdn2d(const float *x, float *out, long long planes, int H, int W, const float *kernel_host, int kh, int kw,
-                               int up, int down, int pad_x0, int pad_x1, int pad_y0, int pad_y1, enarf_stream_t stream) {
-    if (!x || !out || !kernel_host) return host::fail(ENARF_ERR_ARG, "enarf_upfirdn2d: null pointer");
+// The launch decision of enarf_upfirdn2d, kept apart from the launch so that it can be asked without a device
+// (enarf_upfirdn2d_plan): which instantiation, its grid, planes per workgroup, absorbed remainder and LDS tile.
+enum UpfirKernel {          // the order of enarf_upfirdn2d_plan's instantiation index (include/enarf_hip.h)
+    kUfUp2Four, kUfUp2, kUfDown2Four, kUfDown2, kUfWideExt, kUfWide, kUfFourExt, kUfFour, kUfGeneric
+};
+struct UpfirPlan {
+    int kernel, OH, OW, ex, ey, tstride;
+    unsigned gx, gy, gz;
+    long long ppw;
+    size_t lds;
+};
+
+static int upfir_plan(long long planes, int H, int W, int kh, int kw, int up, int down, int pad_x0, int pad_x1, int pad_y0, int pad_y1,
+                      int num_cus, UpfirPlan &pl) {
     if (planes < 0 || H <= 0 || W <= 0) return host::fail(ENARF_ERR_ARG, "enarf_upfirdn2d: bad sizes planes=%lld H=%d W=%d", planes, H, W);
     if (kh <= 0 || kw <= 0 || kh > kUfMaxTaps || kw > kUfMaxTaps)
         return host::fail(ENARF_ERR_UNSUPPORTED, "enarf_upfirdn2d: filter %d x %d outside 1..%d per axis", kh, kw, kUfMaxTaps);
@@ -274,12 +285,8 @@ extern "C" int enarf_upfirdn2d(const float *x, float *out, long long planes, int
         return host::fail(ENARF_ERR_UNSUPPORTED, "enarf_upfirdn2d: up=%d down=%d (built: 1/1, 2/1, 1/2 - what Blur and Upsample use)", up, down);
     const int OH = enarf_upfirdn2d_out_size(H, kh, up, down, pad_y0, pad_y1), OW = enarf_upfirdn2d_out_size(W, kw, up, down, pad_x0, pad_x1);
     if (OH <= 0 || OW <= 0) return host::fail(ENARF_ERR_ARG, "enarf_upfirdn2d: empty output (%d x %d)", OH, OW);
-    if (planes == 0) return 0;
-    UpfirParams p;
-    p.x = x; p.y = out; p.planes = planes; p.H = H; p.W = W; p.OH = OH; p.OW = OW; p.kh = kh; p.kw = kw; p.px0 = pad_x0; p.py0 = pad_y0;
-    for (int i = 0; i < kUfMaxTaps * kUfMaxTaps; ++i) p.kf[i] = 0.0f;
-    for (int i = 0; i < kh; ++i)
-        for (int j = 0; j < kw; ++j) p.kf[i * kw + j] = kernel_host[(kh - 1 - i) * kw + (kw - 1 - j)];
+    if (num_cus <= 0) return host::fail(ENARF_ERR_ARG, "enarf_upfirdn2d: num_cus=%d", num_cus);
+    pl.OH = OH; pl.OW = OW;
     // The plain 4 x 4 blur takes tiles of 128 x 32 outputs (two columns per thread): with 64-column tiles every tile row of a
     // 128-wide map touched three 128-B lines for two lines of outputs (FETCH_SIZE: 1.54x the input, profiles/r03_gan2d_traffic.json).
     // Elsewhere 16 outputs per thread where the tile's input is small (down = 1): twice the loads in flight per wave - the
@@ -290,30 +297,66 @@ extern "C" int enarf_upfirdn2d(const float *x, float *out, long long planes, int
     // a remainder of 1..8 columns / rows beyond whole tiles goes to the last tile column / row (EXT kernels) instead of a tile of its own
     const int rx = OW % tw, ry = OH % th;
     // (not for the decimating form: its tile is 39 KB already and the wider staging took it to one wave per SIMD: 0.25 ms against 0.17)
-    p.ex = (four && up == 1 && down == 1 && rx > 0 && rx <= kUfExt && OW > tw) ? rx : 0;
-    p.ey = (four && up == 1 && down == 1 && ry > 0 && ry <= kUfExt && OH > th) ? ry : 0;
-    const bool ext = p.ex || p.ey;
-    const unsigned gx = (unsigned)(p.ex ? OW / tw : (OW + tw - 1) / tw), gy = (unsigned)(p.ey ? OH / th : (OH + th - 1) / th);
-    if (gy > 65535u) return host::fail(ENARF_ERR_UNSUPPORTED, "enarf_upfirdn2d: output height %d", OH);
+    pl.ex = (four && up == 1 && down == 1 && rx > 0 && rx <= kUfExt && OW > tw) ? rx : 0;
+    pl.ey = (four && up == 1 && down == 1 && ry > 0 && ry <= kUfExt && OH > th) ? ry : 0;
+    const bool ext = pl.ex || pl.ey;
+    pl.gx = (unsigned)(pl.ex ? OW / tw : (OW + tw - 1) / tw);
+    pl.gy = (unsigned)(pl.ey ? OH / th : (OH + th - 1) / th);
+    if (pl.gy > 65535u) return host::fail(ENARF_ERR_UNSUPPORTED, "enarf_upfirdn2d: output height %d", OH);
     // planes per workgroup: enough workgroups for two rounds of 8 per CU, the rest of the planes in each one's pipeline (<= 8)
-    long long ppw = planes * gx * gy / ((long long)(device_cus() > 0 ? device_cus() : 256) * 16);
-    ppw = ppw < 1 ? 1 : (ppw > 8 ? 8 : ppw);
-    long long gzl = (planes + ppw - 1) / ppw;
-    const unsigned gz = (unsigned)(gzl < 65535 ? gzl : 65535);
-    hipStream_t st = (hipStream_t)stream;
+    long long ppw = planes * pl.gx * pl.gy / ((long long)num_cus * 16);
+    pl.ppw = ppw < 1 ? 1 : (ppw > 8 ? 8 : ppw);
+    const long long gzl = (planes + pl.ppw - 1) / pl.ppw;
+    pl.gz = (unsigned)(gzl < 65535 ? gzl : 65535);
     // LDS tile of this configuration: the rows / columns of x that a th x tw output tile can reach, + 1 each for an unaligned start
     const int xr = ext ? kUfExt : 0;
     const int trows = ((th - 1 + xr) * down + kh - 1) / up + 2, tcols = ((tw - 1 + xr) * down + kw - 1) / up + 2;
-    p.tstride = tcols | 1;
-    const size_t lds = (size_t)trows * p.tstride * sizeof(float);
-    if (up == 2 && four) hipLaunchKernelGGL((upfirdn2d_kernel<2, 1, 4, 4, 16>), dim3(gx, gy, gz), dim3(256), lds, st, p);
-    else if (up == 2) hipLaunchKernelGGL((upfirdn2d_kernel<2, 1, 0, 0, 16>), dim3(gx, gy, gz), dim3(256), lds, st, p);
-    else if (down == 2 && four) hipLaunchKernelGGL((upfirdn2d_kernel<1, 2, 4, 4, 8>), dim3(gx, gy, gz), dim3(256), lds, st, p);
-    else if (down == 2) hipLaunchKernelGGL((upfirdn2d_kernel<1, 2, 0, 0, 8>), dim3(gx, gy, gz), dim3(256), lds, st, p);
-    else if (wide && ext) hipLaunchKernelGGL((upfirdn2d_kernel<1, 1, 4, 4, 8, 2, true>), dim3(gx, gy, gz), dim3(256), lds, st, p);
-    else if (wide) hipLaunchKernelGGL((upfirdn2d_kernel<1, 1, 4, 4, 8, 2>), dim3(gx, gy, gz), dim3(256), lds, st, p);
-    else if (four && ext) hipLaunchKernelGGL((upfirdn2d_kernel<1, 1, 4, 4, 16, 1, true>), dim3(gx, gy, gz), dim3(256), lds, st, p);
-    else if (four) hipLaunchKernelGGL((upfirdn2d_kernel<1, 1, 4, 4, 16>), dim3(gx, gy, gz), dim3(256), lds, st, p);
-    else hipLaunchKernelGGL((upfirdn2d_kernel<1, 1, 0, 0, 16>), dim3(gx, gy, gz), dim3(256), lds, st, p);
+    pl.tstride = tcols | 1;
+    pl.lds = (size_t)trows * pl.tstride * sizeof(float);
+    pl.kernel = up == 2 ? (four ? kUfUp2Four : kUfUp2)
+              : down == 2 ? (four ? kUfDown2Four : kUfDown2)
+              : wide ? (ext ? kUfWideExt : kUfWide)
+              : four ? (ext ? kUfFourExt : kUfFour) : kUfGeneric;
+    return 0;
+}
+
+extern "C" int enarf_upfirdn2d_plan(long long planes, int H, int W, int kh, int kw, int up, int down, int pad_x0, int pad_x1, int pad_y0,
+                                    int pad_y1, int num_cus, int *out) {
+    if (!out) return host::fail(ENARF_ERR_ARG, "enarf_upfirdn2d_plan: null pointer");
+    UpfirPlan pl;
+    const int rc = upfir_plan(planes, H, W, kh, kw, up, down, pad_x0, pad_x1, pad_y0, pad_y1, num_cus, pl);
+    if (rc) return rc;
+    const int v[10] = {pl.kernel, (int)pl.gx, (int)pl.gy, (int)pl.gz, (int)pl.ppw, pl.ex, pl.ey, (int)pl.lds, pl.OH, pl.OW};
+    for (int i = 0; i < 10; ++i) out[i] = v[i];
+    return 0;
+}
+
+extern "C" int enarf_upfirdn2d(const float *x, float *out, long long planes, int H, int W, const float *kernel_host, int kh, int kw,
+                               int up, int down, int pad_x0, int pad_x1, int pad_y0, int pad_y1, enarf_stream_t stream) {
+    if (!x || !out || !kernel_host) return host::fail(ENARF_ERR_ARG, "enarf_upfirdn2d: null pointer");
+    UpfirPlan pl;
+    const int rc = upfir_plan(planes, H, W, kh, kw, up, down, pad_x0, pad_x1, pad_y0, pad_y1, device_cus() > 0 ? device_cus() : 256, pl);
+    if (rc) return rc;
+    if (planes == 0) return 0;
+    UpfirParams p;
+    p.x = x; p.y = out; p.planes = planes; p.H = H; p.W = W; p.OH = pl.OH; p.OW = pl.OW; p.kh = kh; p.kw = kw; p.px0 = pad_x0; p.py0 = pad_y0;
+    p.ex = pl.ex; p.ey = pl.ey; p.tstride = pl.tstride;
+    for (int i = 0; i < kUfMaxTaps * kUfMaxTaps; ++i) p.kf[i] = 0.0f;
+    for (int i = 0; i < kh; ++i)
+        for (int j = 0; j < kw; ++j) p.kf[i * kw + j] = kernel_host[(kh - 1 - i) * kw + (kw - 1 - j)];
+    const dim3 grid(pl.gx, pl.gy, pl.gz);
+    const size_t lds = pl.lds;
+    hipStream_t st = (hipStream_t)stream;
+    switch (pl.kernel) {
+    case kUfUp2Four: hipLaunchKernelGGL((upfirdn2d_kernel<2, 1, 4, 4, 16>), grid, dim3(256), lds, st, p); break;
+    case kUfUp2: hipLaunchKernelGGL((upfirdn2d_kernel<2, 1, 0, 0, 16>), grid, dim3(256), lds, st, p); break;
+    case kUfDown2Four: hipLaunchKernelGGL((upfirdn2d_kernel<1, 2, 4, 4, 8>), grid, dim3(256), lds, st, p); break;
+    case kUfDown2: hipLaunchKernelGGL((upfirdn2d_kernel<1, 2, 0, 0, 8>), grid, dim3(256), lds, st, p); break;
+    case kUfWideExt: hipLaunchKernelGGL((upfirdn2d_kernel<1, 1, 4, 4, 8, 2, true>), grid, dim3(256), lds, st, p); break;
+    case kUfWide: hipLaunchKernelGGL((upfirdn2d_kernel<1, 1, 4, 4, 8, 2>), grid, dim3(256), lds, st, p); break;
+    case kUfFourExt: hipLaunchKernelGGL((upfirdn2d_kernel<1, 1, 4, 4, 16, 1, true>), grid, dim3(256), lds, st, p); break;
+    case kUfFour: hipLaunchKernelGGL((upfirdn2d_kernel<1, 1, 4, 4, 16>), grid, dim3(256), lds, st, p); break;
+    default: hipLaunchKernelGGL((upfirdn2d_kernel<1, 1, 0, 0, 16>), grid, dim3(256), lds, st, p); break;
+    }
     return host::check_launch("enarf_upfirdn2d");
 }

@@ -135,6 +135,29 @@ def _upfirdn_call(x: torch.Tensor, filt: Tuple[float, ...], kh: int, kw: int, up
     return out
 
 
+# enarf_upfirdn2d_plan's instantiation index -> template arguments of upfirdn2d_kernel (include/enarf_hip.h)
+UPFIRDN2D_KERNELS = ("2, 1, 4, 4, 16, 1, false", "2, 1, 0, 0, 16, 1, false", "1, 2, 4, 4, 8, 1, false", "1, 2, 0, 0, 8, 1, false",
+                     "1, 1, 4, 4, 8, 2, true", "1, 1, 4, 4, 8, 2, false", "1, 1, 4, 4, 16, 1, true", "1, 1, 4, 4, 16, 1, false",
+                     "1, 1, 0, 0, 16, 1, false")
+
+
+def upfirdn2d_plan(planes: int, H: int, W: int, kh: int, kw: int, up: int = 1, down: int = 1, pad: Sequence[int] = (0, 0),
+                   num_cus: int = 256) -> dict:
+    """The launch upfirdn2d makes for these arguments on a device with `num_cus` CUs (host only, no device needed):
+    kernel (its template arguments), grid, planes per workgroup (ppw), absorbed remainder (ex, ey), LDS bytes, OH, OW."""
+    pads = tuple(int(p) for p in pad)
+    if len(pads) == 2:
+        pads = (pads[0], pads[1], pads[0], pads[1])
+    lib, out = _lib.load(), (C.c_int * 10)()
+    rc = lib.enarf_upfirdn2d_plan(planes, H, W, kh, kw, up, down, *pads, num_cus, out)
+    if rc != 0:                  # not _lib.check: that also reads the device's status word, and a plan needs no device
+        msg = lib.enarf_last_error().decode(errors="replace")
+        raise (NotImplementedError if rc == -2 else ValueError)(f"upfirdn2d_plan: {msg}")
+    v = list(out)
+    return dict(index=v[0], kernel=UPFIRDN2D_KERNELS[v[0]], grid=(v[1], v[2], v[3]), ppw=v[4], ex=v[5], ey=v[6], lds=v[7],
+                OH=v[8], OW=v[9])
+
+
 def adjoint_pads(H: int, W: int, OH: int, OW: int, kh: int, kw: int, up: int, down: int, pads):
     """pads of the adjoint: upfirdn2d(g, flip(k), up = down, down = up, these) maps (OH, OW) back to exactly (H, W)"""
     px0, _, py0, _ = pads

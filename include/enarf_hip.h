@@ -442,6 +442,14 @@ int enarf_bias_act(const float *x, const float *bias, const float *ref, float *o
 int enarf_upfirdn2d_out_size(int in_size, int taps, int up, int down, int pad0, int pad1);
 int enarf_upfirdn2d(const float *x, float *out, long long planes, int H, int W, const float *kernel_host, int kh, int kw,
                     int up, int down, int pad_x0, int pad_x1, int pad_y0, int pad_y1, enarf_stream_t stream);
+/* enarf_upfirdn2d_plan: the launch enarf_upfirdn2d would make for these arguments on a device with `num_cus` CUs, without
+ *   touching a device (the same function decides the launch). On success out[0..9] = instantiation index, grid x, y, z,
+ *   planes per workgroup, remainder columns / rows absorbed by the last tile column / row, dynamic LDS bytes, OH, OW.
+ *   Instantiation index (upfirdn2d_kernel<UP, DOWN, KH, KW, PER, XPT, EXT>): 0 <2,1,4,4,16,1,false>, 1 <2,1,0,0,16,1,false>,
+ *   2 <1,2,4,4,8,1,false>, 3 <1,2,0,0,8,1,false>, 4 <1,1,4,4,8,2,true>, 5 <1,1,4,4,8,2,false>, 6 <1,1,4,4,16,1,true>,
+ *   7 <1,1,4,4,16,1,false>, 8 <1,1,0,0,16,1,false>. Arguments enarf_upfirdn2d refuses are refused here with the same code. */
+int enarf_upfirdn2d_plan(long long planes, int H, int W, int kh, int kw, int up, int down, int pad_x0, int pad_x1, int pad_y0,
+                         int pad_y1, int num_cus, int *out);
 
 #ifdef __cplusplus
 }

@@ -64,6 +64,57 @@ def test_fused_leaky_relu_module_and_no_bias():
     torch.testing.assert_close(op.fused_leaky_relu(xt, m.bias), F.leaky_relu(xt + m.bias.view(1, 8, 1, 1), 0.2) * 2 ** 0.5)
 
 
+def _bias_act_against_float64(x, b, slope, gain=2 ** 0.5):
+    """forward, derivative form (the gradient's kernel: sign from the forward output) and second derivative of the HIP op
+    against the float64 restatement; x may be any CUDA view (it reaches the kernel as it is when contiguous)"""
+    from enarf_gan_amd.libraries.custom_stylegan2 import op
+    g = torch.Generator(device="cuda").manual_seed(x.numel() % 1000)
+    gy = torch.randn(x.shape, device="cuda", generator=g)
+    ggx = torch.randn(x.shape, device="cuda", generator=g)
+    xx = x.detach().requires_grad_(True)
+    gyy = gy.clone().requires_grad_(True)
+    y = op.fused_leaky_relu(xx, b, slope, gain)
+    (gx,) = torch.autograd.grad(y, xx, gyy, create_graph=True)
+    (g2,) = torch.autograd.grad(gx, gyy, ggx)              # d <gx, ggx> / d gy: the derivative form applied again
+    shape = [1, -1] + [1] * (x.dim() - 2)
+    t = x.double() + (b.double().view(shape) if b is not None else 0.0)
+    want_y = third.fused_leaky_relu(x.double(), None if b is None else b.double(), slope, gain)
+    d = gain * torch.where(t > 0, 1.0, slope)
+    assert _rel(y.detach(), want_y) < 1e-6
+    assert _rel(gx.detach(), gy.double() * d) < 1e-6
+    assert _rel(g2, ggx.double() * d) < 1e-6
+
+
+@pytest.mark.parametrize("shape,vec", [((24, 128, 64, 64), True), ((8, 100, 63, 65), False)])
+def test_fused_leaky_relu_grid_stride_loop(shape, vec):
+    """production-sized activations: the grid is capped at 16 workgroups per CU and every thread loops (>= 3 steps here), in
+    the 4-wide form (inner % 4 == 0) and the scalar one (odd inner)"""
+    n = 1
+    for s_ in shape:
+        n *= s_
+    steps = (n // (4 if vec else 1) + _cus() * 16 * 256 - 1) // (_cus() * 16 * 256)
+    assert steps >= 3 and (shape[2] * shape[3] % 4 == 0) == vec
+    g = torch.Generator(device="cuda").manual_seed(3)
+    x = torch.randn(shape, device="cuda", generator=g)
+    b = torch.randn(shape[1], device="cuda", generator=g)
+    _bias_act_against_float64(x, b, 0.2)
+
+
+@pytest.mark.parametrize("slope", [0.2, 0.0, 1.0])
+@pytest.mark.parametrize("bias", [True, False])
+def test_fused_leaky_relu_misaligned_many_channels_and_slopes(slope, bias):
+    """a view one float into its storage (the scalar kernel takes it: the 16-B vector loads need an aligned base), inner = 4
+    with 1 000 channels (the channel changes with every vector), slopes 0 and 1, with and without a bias"""
+    g = torch.Generator(device="cuda").manual_seed(int(slope * 10) + bias)
+    for shape in ((4, 16, 32, 32), (3, 1000, 2, 2)):
+        n = shape[0] * shape[1] * shape[2] * shape[3]
+        store = torch.randn(n + 1, device="cuda", generator=g)
+        b = torch.randn(shape[1], device="cuda", generator=g) if bias else None
+        for x in (store[1:].view(shape), store[:n].view(shape)):          # misaligned (scalar kernel), aligned (VEC = 4)
+            assert x.is_contiguous()
+            _bias_act_against_float64(x, b, slope)
+
+
 # ------------------------------------------------------------------------------------------------------ upfirdn2d
 UPFIRDN_CASES = [(1, 1, (2, 1)), (1, 1, (1, 1)), (2, 1, (2, 1)), (1, 2, (2, 2)), (1, 2, (1, 1)), (1, 1, (-1, 2)), (1, 1, (0, 0, 3, -1)),
                  (2, 1, (0, 0)), (1, 2, (0, 3, 1, 0)), (2, 1, (3, 3)), (1, 2, (5, 4)), (1, 1, (2, 2))]          # the last: 129 out of 128
@@ -77,7 +128,9 @@ def test_upfirdn2d_matches_restatement(up, down, pad, hw, taps_x):
     H, W = hw
     g = torch.Generator().manual_seed(H * 1000 + W + up * 7 + down)
     x = torch.randn(2, 3, H, W, generator=g)
-    k = torch.outer(torch.tensor([1.0, 3.0, 3.0, 1.0]), torch.tensor(taps_x)) / 7.0          # asymmetric: a flip error would show
+    # asymmetric left to right only (the rows are symmetric): a column flip error would show here, a row flip error would not -
+    # test_upfirdn2d_asymmetric_filters covers that
+    k = torch.outer(torch.tensor([1.0, 3.0, 3.0, 1.0]), torch.tensor(taps_x)) / 7.0
     want = third.upfirdn2d(x.double(), k.double(), up=up, down=down, pad=pad)
     got = op.upfirdn2d(x.cuda(), k.cuda(), up=up, down=down, pad=pad)
     assert got.shape == want.shape
@@ -123,6 +176,135 @@ def test_upfirdn2d_many_planes_and_modules():
     torch.testing.assert_close(c[:, :, 2:-2, 2:-2], torch.full((1, 1, 12, 12), 3.0, device="cuda"))
     with pytest.raises(Exception):
         op.upfirdn2d(y.cuda(), k.cuda(), up=2, down=2)
+
+
+def _random_filter(kh, kw, seed):
+    """a filter with no symmetry in either axis: taps of random sign, magnitudes in [0.25, 1.25) (no tap near zero)"""
+    g = torch.Generator().manual_seed(seed)
+    sign = torch.where(torch.rand(kh, kw, generator=g) < 0.5, -1.0, 1.0)
+    return sign * (0.25 + torch.rand(kh, kw, generator=g)) / (kh * kw) ** 0.5
+
+
+def _cus():
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+FILTER_SIZES = [(1, 1), (1, 8), (8, 1), (2, 2), (3, 4), (5, 5), (8, 8), (4, 4)]          # 4 x 4: the unrolled forms
+FILTER_PADS = [(2, 3), (-1, -2), (3, -1, -2, 2)]                                           # positive, negative (a crop), mixed
+
+
+@pytest.mark.parametrize("up,down", [(1, 1), (2, 1), (1, 2)])
+@pytest.mark.parametrize("pad", FILTER_PADS)
+@pytest.mark.parametrize("kh,kw", FILTER_SIZES)
+@pytest.mark.parametrize("hw", [(19, 23), (67, 130)])
+def test_upfirdn2d_asymmetric_filters(up, down, pad, kh, kw, hw):
+    """random non-separable filters of 1 to 8 taps per axis, symmetric in neither: a row or column flip, a transposed index
+    or a tap read from the wrong row of the LDS tile changes the result"""
+    from enarf_gan_amd.libraries.custom_stylegan2 import op
+    H, W = hw
+    k = _random_filter(kh, kw, kh * 10 + kw)
+    x = torch.randn(2, 3, H, W, generator=torch.Generator().manual_seed(H + kh * 100 + kw))
+    want = third.upfirdn2d(x.double(), k.double(), up=up, down=down, pad=pad)
+    got = op.upfirdn2d(x.cuda(), k.cuda(), up=up, down=down, pad=pad)
+    assert got.shape == want.shape
+    assert _rel(got, want) < 2e-6
+
+
+@pytest.mark.parametrize("up,down,pad", [(1, 1, (2, 1)), (2, 1, (2, 1)), (1, 2, (2, 2)), (1, 1, (-1, 2)), (1, 2, (1, 1)), (2, 1, (0, 3, 1, 0))])
+@pytest.mark.parametrize("kh,kw", [(4, 4), (3, 5)])
+def test_upfirdn2d_backward_and_second_derivative_asymmetric(up, down, pad, kh, kw):
+    """the adjoint is upfirdn2d with the filter flipped in both axes, up / down swapped and its own pads (op._UpFirDn2d):
+    with a filter symmetric in neither axis a wrong flip or pad shows in the first and second derivative"""
+    from enarf_gan_amd.libraries.custom_stylegan2 import op
+    g = torch.Generator().manual_seed(13)
+    x = torch.randn(2, 2, 21, 18, generator=g)
+    k = _random_filter(kh, kw, 7 * kh + kw)
+
+    def run(fn, dev, dt):
+        xx = x.to(dev, dt).requires_grad_(True)
+        y = fn(xx, k.to(dev, dt), up=up, down=down, pad=pad)
+        gy = torch.randn(y.shape, generator=torch.Generator().manual_seed(5)).to(dev, dt)
+        (gx,) = torch.autograd.grad((y * y * gy).sum(), xx, create_graph=True)
+        (ggx,) = torch.autograd.grad(gx.pow(2).sum(), xx)
+        return y.detach().cpu(), gx.detach().cpu(), ggx.cpu()
+
+    want = run(third.upfirdn2d, "cpu", torch.float64)
+    got = run(op.upfirdn2d, "cuda", torch.float32)
+    for a, b, tol in zip(got, want, (2e-6, 1e-5, 1e-4)):
+        assert a.shape == b.shape and _rel(a, b) < tol
+
+
+# Plan boundaries (enarf_upfirdn2d_plan), 6 planes each: (H, W, kh, kw, up, down, pad, instantiation index at 256 CUs).
+# With pad (1, 2) a 4 x 4 blur keeps the size, so H, W are the output's. tests/test_kernel_coverage_cpu.py checks that these
+# plan what their comments say.
+UPFIRDN_BOUNDARY_CASES = [
+    (65, 40, 4, 4, 1, 1, (1, 2), 6), (72, 40, 4, 4, 1, 1, (1, 2), 6),       # narrow-tall: a 1- and an 8-row remainder absorbed
+    (73, 40, 4, 4, 1, 1, (1, 2), 7),                                        # 9 rows: a tile of their own, not EXT
+    (66, 40, 4, 4, 1, 1, (2, 2), 6),                                        # 67 x 41: a 3-row remainder
+    (33, 129, 4, 4, 1, 1, (1, 2), 4), (40, 136, 4, 4, 1, 1, (1, 2), 4),     # wide: 1 and 8 columns and rows absorbed
+    (41, 137, 4, 4, 1, 1, (1, 2), 5),                                       # 9 and 9: not EXT
+    (20, 64, 4, 4, 1, 1, (1, 2), 7), (20, 65, 4, 4, 1, 1, (1, 2), 5),       # OW = the 64-column tile, and one more (wide)
+    (20, 128, 4, 4, 1, 1, (1, 2), 5), (20, 129, 4, 4, 1, 1, (1, 2), 4),     # OW = the 128-column tile, and one more
+    (20, 70, 4, 4, 1, 1, (1, 2), 5), (20, 131, 4, 4, 1, 1, (1, 2), 4),      # short and wide: OW in 65..72; 3 columns absorbed
+    (33, 128, 4, 4, 1, 1, (1, 2), 4), (65, 64, 4, 4, 1, 1, (1, 2), 6),      # a whole tile column, a 1-row remainder absorbed
+    (32, 32, 4, 4, 2, 1, (2, 1), 0), (16, 32, 4, 4, 2, 1, (2, 2), 0),       # up-sampler: 64 x 64 out, 33 x 65
+    (33, 32, 3, 4, 2, 1, (2, 1), 1),                                        # generic up-sampler, 67 x 64
+    (64, 128, 4, 4, 1, 2, (1, 1), 2), (66, 130, 4, 4, 1, 2, (1, 1), 2),     # decimator: 32 x 64 out (a whole tile), 33 x 65
+    (66, 130, 5, 3, 1, 2, (1, 1), 3), (66, 128, 5, 3, 1, 2, (1, 1), 3),     # generic decimator: 32 x 65, 32 x 64
+    (64, 64, 3, 4, 1, 1, (1, 2), 8), (65, 65, 3, 4, 1, 1, (1, 2), 8)]       # generic filter: 65 x 64, 66 x 65
+
+
+@pytest.mark.parametrize("case", UPFIRDN_BOUNDARY_CASES)
+def test_upfirdn2d_plan_boundaries(case):
+    from enarf_gan_amd.libraries.custom_stylegan2 import op
+    H, W, kh, kw, up, down, pad, _ = case
+    k = _random_filter(kh, kw, H * W)
+    x = torch.randn(2, 3, H, W, generator=torch.Generator().manual_seed(H * 1000 + W))
+    want = third.upfirdn2d(x.double(), k.double(), up=up, down=down, pad=pad)
+    got = op.upfirdn2d(x.cuda(), k.cuda(), up=up, down=down, pad=pad)
+    assert got.shape == want.shape
+    assert _rel(got, want) < 2e-6
+
+
+# The multi-plane pipeline, every instantiation at ppw >= 2: (planes, H, W, kh, kw, up, down, pad, index at 256 CUs). Plane
+# counts are not multiples of the planes per workgroup; the last case passes the 65 535 cap of grid z.
+UPFIRDN_PIPELINE_CASES = [
+    (2 * 4096 + 3, 10, 12, 4, 4, 2, 1, (2, 1), 0),
+    (3 * 4096 + 1, 9, 13, 3, 4, 2, 1, (1, 2), 1),
+    (5 * 4096 + 2, 30, 34, 4, 4, 1, 2, (1, 1), 2),
+    (8 * 4096 + 7, 20, 21, 5, 3, 1, 2, (2, 1), 3),
+    (2 * 4096 + 1, 38, 128, 4, 4, 1, 1, (2, 2, 1, 2), 4),          # 38 x 129 out: a 6-row and a 1-column remainder absorbed
+    (3 * 4096 + 2, 20, 100, 4, 4, 1, 1, (2, 1), 5),
+    (2 * 4096 + 1, 66, 40, 4, 4, 1, 1, (2, 2), 6),                 # the narrow-tall remainder kernel
+    (4 * 4096 + 3, 20, 24, 4, 4, 1, 1, (2, 1), 7),
+    (6 * 4096 + 5, 16, 18, 3, 4, 1, 1, (1, 1), 8),
+    (65535 * 8 + 13, 3, 3, 4, 4, 1, 1, (2, 1), 7)]                 # gz capped: workgroups stride over more than 8 planes
+
+
+@pytest.mark.parametrize("case", UPFIRDN_PIPELINE_CASES)
+def test_upfirdn2d_pipeline_planes(case):
+    """A workgroup filters plane k out of LDS while plane k + gz's loads are in flight. upfirdn2d is linear and scaling by a
+    power of two is exact (no subnormals here: |x| >= 0.5, taps >= 0.25), so plane k = 2^(k mod 7 - 3) * X[k mod 5] must give
+    2^(k mod 7 - 3) times the output of X[k mod 5] bit for bit - neighbouring planes differ in both factors, so a tile of the
+    wrong plane, or a stale one, fails. The five base planes alone (one per workgroup, the same instantiation) are checked
+    against the oracle."""
+    from enarf_gan_amd.libraries.custom_stylegan2 import op
+    planes, H, W, kh, kw, up, down, pad, _ = case
+    plan = op.upfirdn2d_plan(planes, H, W, kh, kw, up, down, pad, num_cus=_cus())
+    assert plan["ppw"] >= 2 and planes % plan["ppw"] != 0, plan
+    g = torch.Generator().manual_seed(planes)
+    base = torch.where(torch.rand(5, 1, H, W, generator=g) < 0.5, -1.0, 1.0) * (0.5 + torch.rand(5, 1, H, W, generator=g))
+    k = _random_filter(kh, kw, planes)
+    kd = k.cuda()
+    y_base = op.upfirdn2d(base.cuda(), kd, up=up, down=down, pad=pad)
+    assert _rel(y_base, third.upfirdn2d(base.double(), k.double(), up=up, down=down, pad=pad)) < 2e-6
+    idx = torch.arange(planes, device="cuda")
+    scale = torch.pow(2.0, (idx % 7 - 3).float())
+    x = (base.cuda()[idx % 5, 0] * scale[:, None, None])[:, None]
+    y = op.upfirdn2d(x, kd, up=up, down=down, pad=pad)
+    want = y_base[idx % 5, 0] * scale[:, None, None]
+    bad = (y[:, 0] != want).flatten(1).any(1).nonzero().flatten()
+    assert bad.numel() == 0, f"{bad.numel()} planes differ, first {bad[:8].tolist()} (plan {plan})"
 
 
 # ---------------------------------------------------------------------------------------- networks vs the reference

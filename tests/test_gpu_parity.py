@@ -78,11 +78,24 @@ def test_sampler_golden_fwd_bwd(ops):
     assert_close(_cpu(gg)[:, :, 0].permute(0, 2, 1), g["grad_position"], "sampler grad_grid", 1e-5)
 
 
-@pytest.mark.parametrize("C", [32, 8, 5])
+@pytest.mark.parametrize("C", [32, 8, 5, 16, 64])
 def test_sampler_fast_path_vs_oracle(ops, C):
     g = torch.Generator().manual_seed(C)
     inp = torch.randn(2, 3 * C, 40, 56, generator=g)
     grid = torch.rand(2, 777, 1, 3, generator=g) * 2.2 - 1.1
+    ref = O.triplane_sampler_forward(inp, grid)
+    for ws in (True, False):
+        out = ops.triplane_sample_fwd(inp.cuda(), grid.cuda(), use_workspace=ws)
+        assert_close(_cpu(out), ref, f"sampler fwd C={C} ws={ws}", 1e-5)
+
+
+@pytest.mark.parametrize("C", [16, 64])
+def test_sampler_fast_path_channel_widths_at_tile_edges(ops, C):
+    """the channel-last widths C = 16 (pack_kernel<16>, sample_fwd_cl<2>: 128 points per workgroup) and C = 64 (<64>, <8>: 32
+    points), batch 2, a point count that is a multiple of neither and W = 100: the pack's 64-column tiles end mid-tile"""
+    g = torch.Generator().manual_seed(C + 1)
+    inp = torch.randn(2, 3 * C, 37, 100, generator=g)
+    grid = torch.rand(2, 1037, 1, 3, generator=g) * 2.2 - 1.1
     ref = O.triplane_sampler_forward(inp, grid)
     for ws in (True, False):
         out = ops.triplane_sample_fwd(inp.cuda(), grid.cuda(), use_workspace=ws)
@@ -236,6 +249,27 @@ def test_query_bf16_mode_is_close(ops):
     d16, c16 = ds.query(pts, mlp_mode="bf16")
     assert rel_err(_cpu(d16), _cpu(d32)).max() < 8e-2
     assert rel_err(_cpu(c16), _cpu(c32)).max() < 8e-2
+
+
+@pytest.mark.parametrize("mode", ["bf16x3", "bf16"])
+def test_query_debug_and_production_kernels_in_bf16_modes(ops, mode):
+    """query_kernel with and without the debug outputs in both bf16 modes: the production kernel gives the debug kernel's
+    bits, the debug taps are bit-exact against the oracle, values within the mode's bound (bf16: the 8e-2 of
+    test_query_bf16_mode_is_close)"""
+    g = load_golden("query_b2_p23")
+    sc = Scene(64, 2, "center_fixed", 256)
+    ds = DeviceScene(sc)
+    pts = torch.from_numpy(g["points"])
+    den, col, vb, dc, dw = ds.query(pts, mlp_mode=mode, debug=True)
+    pden, pcol, pvb = ds.query(pts, mlp_mode=mode, need_valid=True)
+    assert torch.equal(pvb, vb) and torch.equal(pden, den) and torch.equal(pcol, col)
+    oden, ocol, ovalid, taps = O.query(pts, sc.pose_scaled, sc.scale, sc.cpose, sc.raw["tri_plane"], sc.weights(), return_taps=True)
+    assert np.array_equal(_cpu(vb).numpy().view(np.uint32), bits_of(ovalid))
+    assert torch.equal(_cpu(dc), taps["canonical"])
+    assert_close(_cpu(dw), taps["weight"], "part probability", 1e-5)
+    tol = MODE_TOL.get(mode, 8e-2)
+    assert_close(_cpu(den), oden, f"density {mode}", tol)
+    assert_close(_cpu(col), ocol, f"colour {mode}", tol)
 
 
 def test_query_ragged_and_empty(ops):
@@ -603,6 +637,36 @@ def test_both_march_kernels_give_the_same_bits(ops, S, B, Nc, Nf, n0, nr):
     assert nr < 100 or float(a.mask.max()) > 0.05
     with pytest.raises(KeyError):
         ds.render(coord, Nc, Nf, None, march="fastest")
+
+
+@pytest.mark.parametrize("mode", ["bf16x3", "bf16"])
+@pytest.mark.parametrize("Nc,Nf", [(24, 32), (16, 128)])
+def test_bf16_modes_both_march_kernels_vs_oracle(ops, mode, Nc, Nf):
+    """render_kernel (march="ray") and march_kernel (march="task") in the two bf16 modes, at one sample per lane and at two
+    (Nf = 128): against the oracle with the same fine samples, within the mode's bound (bf16: 8e-2, as for its query), and
+    equal to each other bit for bit, as test_both_march_kernels_give_the_same_bits requires of the other modes"""
+    sc = Scene(32, 1, "center_fixed", 20)
+    ds = DeviceScene(sc)
+    coord = sc.raw["image_coord"][..., 32 * 12:32 * 12 + 96].contiguous()
+    bins = torch.rand(1, 96, Nf, generator=torch.Generator().manual_seed(Nc + Nf)).sort(-1).values
+    rc, rm, rd = sc.oracle_render(coord, Nc, Nf, bins, taps=False)
+    assert float(rm.max()) > 0.1
+    tol = MODE_TOL.get(mode, 8e-2)
+    outs = [ds.render(coord, Nc, Nf, bins, mlp_mode=mode, march=m, count=True) for m in ("ray", "task")]
+    for o, m in zip(outs, ("ray", "task")):
+        assert_close(_cpu(o.color), rc, f"colour {mode} {m}", tol)
+        assert_close(_cpu(o.mask), rm, f"mask {mode} {m}", tol)
+        assert_close(_cpu(o.disparity), rd, f"disparity {mode} {m}", tol)
+    a, b = outs
+    for name in ("color", "mask", "disparity", "fine_weights", "fine_depth"):
+        assert torch.equal(getattr(a, name), getattr(b, name)), name
+    assert torch.equal(a.counters[:5], b.counters[:5])
+    # in-kernel importance sampling: the same draws and bits from both kernels
+    a = ds.render(coord, Nc, Nf, None, seed=5, mlp_mode=mode, march="ray", count=True, return_bins=True)
+    b = ds.render(coord, Nc, Nf, None, seed=5, mlp_mode=mode, march="task", count=True, return_bins=True)
+    assert torch.equal(a.taps["bins"], b.taps["bins"])
+    for name in ("color", "mask", "disparity", "fine_weights", "fine_depth"):
+        assert torch.equal(getattr(a, name), getattr(b, name)), name
 
 
 def test_steps_on_two_streams_do_not_interfere(ops):

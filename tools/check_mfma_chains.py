@@ -104,18 +104,40 @@ def regs(tok):
     return None          # inline constant / literal
 
 
+def _code_objects(path, work):
+    """unbundle the gfx950 code objects of a .so into `work`; their paths"""
+    lib = os.path.join(work, os.path.basename(path))
+    shutil.copy(path, lib)
+    subprocess.run([OBJDUMP, "--offloading", lib], check=True, capture_output=True)
+    objs = sorted(f for f in os.listdir(work) if "amdgcn" in f)
+    if not objs:
+        raise SystemExit(f"{path}: no gfx950 code object found")
+    return [os.path.join(work, o) for o in objs]
+
+
+def kernel_symbols(path):
+    """the demangled names of every kernel instantiation in the library: its `.kd` (kernel descriptor) symbols"""
+    work = tempfile.mkdtemp(prefix="enarf_kd_")
+    try:
+        names = set()
+        for o in _code_objects(path, work):
+            txt = subprocess.run([OBJDUMP, "-t", "-C", o], check=True, capture_output=True, text=True).stdout
+            for line in txt.splitlines():
+                if line.endswith(" (.kd)"):          # "<value> <flags> <section>\t<size> [.protected] <name> (.kd)"
+                    name = line.split("\t", 1)[1].split(None, 1)[1][: -len(" (.kd)")]
+                    names.add(re.sub(r"^\.(protected|hidden|internal) ", "", name))
+        return sorted(names)
+    finally:
+        shutil.rmtree(work, ignore_errors=True)
+
+
 def check(path):
     work = tempfile.mkdtemp(prefix="enarf_isa_")
     try:
-        lib = os.path.join(work, os.path.basename(path))
-        shutil.copy(path, lib)
-        subprocess.run([OBJDUMP, "--offloading", lib], check=True, capture_output=True)
-        objs = sorted(f for f in os.listdir(work) if "amdgcn" in f)
-        if not objs:
-            raise SystemExit(f"{path}: no gfx950 code object found")
+        objs = _code_objects(path, work)
         problems, n_mfma, n_kernels = [], 0, 0
         for o in objs:
-            txt = subprocess.run([OBJDUMP, "-d", os.path.join(work, o)], check=True, capture_output=True, text=True).stdout
+            txt = subprocess.run([OBJDUMP, "-d", o], check=True, capture_output=True, text=True).stdout
             kernel, recent, clock, body = None, [], 0, []
             for line in txt.splitlines() + ["0 <end>:"]:
                 m = re.match(r"^[0-9a-f]+ <(\S+)>:", line)

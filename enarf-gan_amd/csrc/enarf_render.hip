@@ -429,11 +429,13 @@ __device__ __forceinline__ void ray_setup_block(const enarf_render_args &a, cons
     const float *Ki = a.inv_intrinsics + (size_t)b * 9;
     const float u = coord[rc], v = coord[n + rc], w = coord[2 * n + rc];
     const float k0 = Ki[0], k1 = Ki[1], k2 = Ki[2], k3 = Ki[3], k4 = Ki[4], k5 = Ki[5], k6 = Ki[6], k7 = Ki[7], k8 = Ki[8];
+    float own_z = 0.0f;   // RAW: z of this thread's part centre, fr[11] - the arithmetic of part_centre_z, so the same bits
     if constexpr (RAW) {
         if (tid < P) {
             float fr[16];
             compute_part_frame(raw, b, tid, fr);
             for (int i = 0; i < 16; ++i) l_parts[tid * kLdsPartStride + i] = fr[i];
+            own_z = fr[11];
         }
     } else {
         for (int i = tid; i < P * kPartStride; i += 256)
@@ -444,12 +446,16 @@ __device__ __forceinline__ void ray_setup_block(const enarf_render_args &a, cons
         __syncthreads();
     } else {   // batch-global near / far planes (rendering.py:15-17): min / max of every part centre's z
         float mn = 3.0e38f, mx = -3.0e38f;
-        for (int i = tid; i < a.B * P; i += 256) {
-            float z;
-            if constexpr (RAW) z = part_centre_z(raw, i / P, i % P);
-            else z = a.parts[(size_t)i * kPartStride + 11];
-            mn = fminf(mn, z);
-            mx = fmaxf(mx, z);
+        if (RAW && a.B == 1) {   // the block's own frames are the whole batch: no second walk of parents -> poses
+            if (tid < P) { mn = fminf(mn, own_z); mx = fmaxf(mx, own_z); }
+        } else {
+            for (int i = tid; i < a.B * P; i += 256) {
+                float z;
+                if constexpr (RAW) z = part_centre_z(raw, i / P, i % P);
+                else z = a.parts[(size_t)i * kPartStride + 11];
+                mn = fminf(mn, z);
+                mx = fmaxf(mx, z);
+            }
         }
         near_far_reduce(mn, mx, l_red, tid);
     }
@@ -553,11 +559,39 @@ __device__ __forceinline__ void ray_setup_block(const enarf_render_args &a, cons
     const int q = ws_band_of(a.B, n, b, blk);
     unsigned int *wsh = reinterpret_cast<unsigned int *>(reinterpret_cast<char *>(a.workspace) + ws_header_off(a.ws_epoch));
     __syncthreads();
-    if (tid < kFile) {
-        const int tot = l_cnt[tid] + l_cnt[kFile + tid] + l_cnt[2 * kFile + tid] + l_cnt[3 * kFile + tid];
-        const int lid = (tid < kClasses) ? q * kClasses + tid : ws_missed_list(q);
-        l_cnt[4 * kFile + tid] = tot ? (int)atomicAdd(wsh + kWsCountsOff + lid, (unsigned int)tot) : 0;
-        if (tot) atomicAdd(wsh + ((tid < kClasses) ? 1 : 2), (unsigned int)tot);     // [1] rays to march, [2] rays that miss every cube
+    // Every block's reservations meet on the same few header words, where device-scope atomics queue one behind the other
+    // (C1, stand-alone set-up pass: 15.8 us, 10.4 without them; profiles/r04_premarch_roles.log), so a block issues as few
+    // as it can: the two counters of a class pair are adjacent u32 in one aligned u64 and take ONE 64-bit add (no carry
+    // crosses: a count stays below 2^32), whose old value holds both bases; [1] takes the sum of the four classes in one
+    // add (11.5 us).
+    static_assert(kClasses == 4 && (kWsCountsOff + kClasses) % 2 == 0 && kWsHeaderBytes % 8 == 0, "class-pair counters");
+    if (tid < 4) {
+        const auto total = [&](int c) { return l_cnt[c] + l_cnt[kFile + c] + l_cnt[2 * kFile + c] + l_cnt[3 * kFile + c]; };
+        if (tid < 2) {
+            const int c = 2 * tid, t0 = total(c), t1 = total(c + 1);
+            unsigned int *cnt = wsh + kWsCountsOff + q * kClasses + c;
+            int b0 = 0, b1 = 0;
+            if ((reinterpret_cast<uintptr_t>(cnt) & 7u) == 0u) {
+                if (t0 | t1) {
+                    const unsigned long long old = atomicAdd(reinterpret_cast<unsigned long long *>(cnt),
+                                                             ((unsigned long long)(unsigned)t1 << 32) | (unsigned)t0);
+                    b0 = (int)(unsigned)old;
+                    b1 = (int)(unsigned)(old >> 32);
+                }
+            } else {   // a workspace that is only 4-byte aligned
+                if (t0) b0 = (int)atomicAdd(cnt, (unsigned int)t0);
+                if (t1) b1 = (int)atomicAdd(cnt + 1, (unsigned int)t1);
+            }
+            l_cnt[4 * kFile + c] = b0;
+            l_cnt[4 * kFile + c + 1] = b1;
+        } else if (tid == 2) {   // live rays without a candidate part: their list, and [2] rays that miss every cube
+            const int tm = total(kClasses);
+            l_cnt[4 * kFile + kClasses] = tm ? (int)atomicAdd(wsh + kWsCountsOff + ws_missed_list(q), (unsigned int)tm) : 0;
+            if (tm) atomicAdd(wsh + 2, (unsigned int)tm);
+        } else {                 // [1] rays to march
+            const int tc = total(0) + total(1) + total(2) + total(3);
+            if (tc) atomicAdd(wsh + 1, (unsigned int)tc);
+        }
     }
     __syncthreads();
     if (file_it) {

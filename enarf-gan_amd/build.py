@@ -1,7 +1,7 @@
-"""Build recipe of libenarf_hip.so (hipcc, gfx950 only), in-tree under csrc/.
+"""Build recipe of libenarf_hip.so and libenarf_mesh.so (hipcc, gfx950 only), in-tree under csrc/.
 
-`python -m enarf_gan_amd.build` or `build()`; `__graft_entry__.build()` calls this. The .so is
-git-ignored but travels to the GPU box with the repo snapshot.
+`python -m enarf_gan_amd.build` or `build()`; `__graft_entry__.build()` calls this. The .so files are
+git-ignored but travel to the GPU box with the repo snapshot.
 """
 from __future__ import annotations
 
@@ -17,6 +17,10 @@ LIB = os.path.join(CSRC, "libenarf_hip.so")
 SOURCES = ["enarf_render.hip", "enarf_render_bwd.hip", "enarf_sampler.hip", "enarf_raysample.hip", "enarf_gan_ops.hip"]
 # every header next to the sources is a dependency of every object (a list by name went stale when enarf_tasks.h was added)
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(ROOT, "include", "enarf_hip.h")]
+# marching cubes (include/enarf_mesh.h) is a library of its own: its kernels are not part of libenarf_hip.so's inventory
+MESH_SOURCES = ["enarf_mesh.hip"]
+MESH_LIB = os.path.join(CSRC, "libenarf_mesh.so")
+MESH_HEADERS = [os.path.join(ROOT, "include", "enarf_mesh.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
          "-I", os.path.join(ROOT, "include"), "-I", CSRC]
 
@@ -26,15 +30,19 @@ def _newer(a: str, b: str) -> bool:
 
 
 def build(force: bool = False, verbose: bool = False, extra_flags=()) -> str:
+    """Build both libraries incrementally; returns the path of libenarf_hip.so (MESH_LIB is next to it)."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     deps = [os.path.join(CSRC, h) if not os.path.isabs(h) else h for h in HEADERS] + [os.path.abspath(__file__)]
-    objs, jobs = [], []
-    for src in SOURCES:
-        s = os.path.join(CSRC, src)
-        o = os.path.join(CSRC, src.replace(".hip", ".o"))
-        objs.append(o)
-        if force or _newer(s, o) or any(_newer(d, o) for d in deps):
-            jobs.append([hipcc, *FLAGS, *extra_flags, "-c", s, "-o", o])
+    libs, jobs = [], []
+    for lib, sources, lib_deps in ((LIB, SOURCES, deps), (MESH_LIB, MESH_SOURCES, deps + MESH_HEADERS)):
+        objs, n_jobs = [], len(jobs)
+        for src in sources:
+            s = os.path.join(CSRC, src)
+            o = os.path.join(CSRC, src.replace(".hip", ".o"))
+            objs.append(o)
+            if force or _newer(s, o) or any(_newer(d, o) for d in lib_deps):
+                jobs.append([hipcc, *FLAGS, *extra_flags, "-c", s, "-o", o])
+        libs.append((lib, objs, len(jobs) > n_jobs))
 
     def run(cmd):
         if verbose:
@@ -45,10 +53,11 @@ def build(force: bool = False, verbose: bool = False, extra_flags=()) -> str:
         if verbose and r.stderr.strip():
             print(r.stderr, file=sys.stderr)
 
-    with ThreadPoolExecutor(max_workers=len(SOURCES)) as ex:
+    with ThreadPoolExecutor(max_workers=len(SOURCES) + len(MESH_SOURCES)) as ex:
         list(ex.map(run, jobs))
-    if jobs or force or not os.path.exists(LIB):
-        run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB, *objs])
+    for lib, objs, rebuilt in libs:
+        if rebuilt or force or not os.path.exists(lib) or any(_newer(o, lib) for o in objs):
+            run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib, *objs])
     return LIB
 
 

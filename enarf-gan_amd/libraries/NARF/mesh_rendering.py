@@ -3,8 +3,9 @@
 The reference builds the (2/voxel_size + 1)^3 grid on the host, pushes it through
 `calc_density_and_color_from_camera_coord_v2` in `render_bs` chunks and hands the volume to `mcubes`. Here the lattice
 is generated inside `enarf_query_fwd` (lattice mode, density only, one launch; or chunk by chunk from device tensors when
-`chunk` is given); the volume stays on the device. Marching cubes (`mcubes`) and the rasteriser (`pytorch3d`) are third-party and not part of this package:
-`create_mesh` raises ImportError where the reference would, after the volume is available from `density_volume`.
+`chunk` is given); the volume stays on the device. `create_mesh` keeps the reference's third-party stages (`mcubes`,
+`pytorch3d`) and raises ImportError where the reference would. `extract_mesh` is the same mesh built on the device:
+`density_volume` -> `marching_cubes` (libenarf_mesh.so) -> the reference's transform; `export_obj` writes it out.
 """
 from __future__ import annotations
 
@@ -13,6 +14,7 @@ from typing import Dict
 import torch
 
 from ... import ops
+from ... import _mesh_lib
 
 
 def _grid_chunk(D: int, start: int, stop: int, center: torch.Tensor, scale: float, dev: torch.device) -> torch.Tensor:
@@ -81,6 +83,48 @@ def create_mesh(model, pose_to_camera, center, voxel_size=0.003, mesh_th=15, mod
     vertices = torch.tensor((vertices - cube) * voxel_size, device=dev).float() + center[:, :, 0]
     triangles = torch.tensor(triangles.astype("int64")).to(dev)
     return vertices, triangles, Textures(verts_rgb=torch.ones_like(vertices)[None])
+
+
+def marching_cubes(volume: torch.Tensor, isovalue: float):
+    """Marching cubes on the device (libenarf_mesh.so), same argument order as `mcubes.marching_cubes`.
+
+    volume: contiguous fp32 (X, Y, Z) device tensor, X, Y, Z >= 2 and X*Y*Z < 2^31. Returns (vertices (V, 3) fp32 in
+    index units, triangles (T, 3) int64) on the same device. A lattice point is inside iff its value > isovalue (NaN is
+    outside). One vertex per crossing lattice edge (p, p + e_a), at p + t e_a with t = (iso - v[p]) / (v[p + e_a] - v[p])
+    in fp32 (PyMCubes' interpolation), ordered by p's C-order index and then by a; triangles are ordered by cube (C order)
+    and then by the case table, and (v1 - v0) x (v2 - v0) points from inside to outside (toward lower values).
+
+    The table (csrc/enarf_mc_table.h, generated by tools/gen_mc_table.py) is face-consistent, so the surface has no
+    cracks. It differs from PyMCubes' classic Lorensen table only in cubes with an ambiguous face: the vertex set is the
+    same, the triangles there may differ, and PyMCubes' exact triangle order is not reproduced. No CPU fallback."""
+    return _mesh_lib.marching_cubes(volume, isovalue)
+
+
+@torch.no_grad()
+def extract_mesh(model, pose_to_camera: torch.Tensor, center: torch.Tensor, voxel_size: float = 0.003, mesh_th: float = 15,
+                 model_input: Dict = {}):
+    """create_mesh (mesh_rendering.py:50-81) on the device: density_volume -> marching_cubes -> the reference's
+    transform (vertices - cube) * voxel_size + center, in fp32. Returns (vertices (V, 3), triangles (T, 3) int64) on
+    pose_to_camera's device; no texture (the rasteriser that would use it is third-party)."""
+    if pose_to_camera.device.type != "cuda":
+        raise _mesh_lib.EnarfHipError("extract_mesh runs on the device (there is no CPU fallback)")
+    density = density_volume(model, pose_to_camera, center, voxel_size, model_input)
+    cube = int(1 / voxel_size)
+    vertices, triangles = marching_cubes(density, mesh_th)
+    vertices = (vertices - cube) * voxel_size + center.to(vertices.device).float()[:, :, 0]
+    return vertices, triangles
+
+
+def export_obj(vertices, triangles, path: str) -> None:
+    """Plain-text Wavefront OBJ ("v x y z" lines, then "f a b c" with 1-based indices), as mcubes.export_obj writes."""
+    import numpy as np
+    v = vertices.detach().cpu().numpy() if isinstance(vertices, torch.Tensor) else np.asarray(vertices)
+    f = triangles.detach().cpu().numpy() if isinstance(triangles, torch.Tensor) else np.asarray(triangles)
+    with open(path, "w") as fh:
+        for x in v:
+            fh.write("v %r %r %r\n" % (float(x[0]), float(x[1]), float(x[2])))
+        for t in f.astype(np.int64) + 1:
+            fh.write("f %d %d %d\n" % (t[0], t[1], t[2]))
 
 
 def render_mesh_(meshes, intrinsics, img_size, render_size=512):

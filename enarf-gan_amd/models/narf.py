@@ -332,6 +332,13 @@ class TriPlaneNARF(nn.Module):
         center, pose_parts, model_input = self._mesh_inputs(pose_to_camera, z, z_rend, bone_length, truncation_psi)
         return density_volume(self, pose_parts, center, voxel_size, model_input)
 
+    def extract_mesh(self, pose_to_camera, z, z_rend, bone_length, voxel_size=0.003, mesh_th=15, truncation_psi=0.4):
+        """The mesh of render_mesh / create_mesh built on the device: density sweep -> HIP marching cubes -> the
+        reference's transform (mesh_rendering.extract_mesh). Returns (vertices (V, 3), triangles (T, 3) int64)."""
+        from ..libraries.NARF.mesh_rendering import extract_mesh
+        center, pose_parts, model_input = self._mesh_inputs(pose_to_camera, z, z_rend, bone_length, truncation_psi)
+        return extract_mesh(self, pose_parts, center, voxel_size, mesh_th, model_input)
+
     def _mesh_inputs(self, pose_to_camera, z, z_rend, bone_length, truncation_psi):
         if not ((z is None or z.shape[0] == 1) and (bone_length is None or bone_length.shape[0] == 1)):
             raise AssertionError("render_mesh takes one sample (base.py:67-68)")

@@ -9,15 +9,10 @@ namespace enarf {
 // =================================================================================================
 // LDS staging shared by the query and render kernels
 // =================================================================================================
-// dynamic LDS layout (floats): [mlp section][bias 144][parts P*20][canon P*12][scratch kScratchFloats]
-constexpr int kScratchFloats = 1664;
+// dynamic LDS layout (floats): [mlp section][bias 144][parts P*20][canon P*12][scratch kScratchFloats (below)]
 template <int MODE>
 __host__ __device__ constexpr int lds_mlp_floats() {
     return (MODE == ENARF_MLP_F32) ? PK_B1 : PKH_SHORTS / 2;
-}
-template <int MODE>
-__host__ __device__ inline int lds_total_floats(int P) {
-    return lds_mlp_floats<MODE>() + 144 + P * kLdsPartStride + P * kLdsCanonStride + kScratchFloats;
 }
 
 template <int MODE>
@@ -204,6 +199,41 @@ struct RayQueue {
     __device__ __forceinline__ int get(int slot) const { return l_q[slot * kQSlotInts]; }
     __device__ __forceinline__ RayRec rec(int slot) const { return *reinterpret_cast<const RayRec *>(l_q + slot * kQSlotInts + 4); }
 };
+
+// ---- LDS record of one ray in the march (32-bit words): a slot of march_kernel, the per-ray scratch of render_kernel ---
+constexpr int kMaxSamples = 128;          // samples per pass (two per lane in the lane = sample stages above 64)
+constexpr int SL_CTL = 0;                 // control word, see pack_ctl (march_kernel)
+constexpr int SL_DONE = 1;                // completed tiles of the current stage
+constexpr int SL_RID = 2;                 // global ray id (image * n + ray)
+constexpr int SL_NCAND = 3;
+constexpr int SL_REC = 4;                 // RayRec, 8 words (16-byte aligned)
+constexpr int SL_CAND = 12;               // candidate part ids, 32 ints
+constexpr int SL_SKIP = 44;               // early-termination flags per fine tile, 8 ints
+constexpr int SL_NEXT_STATE = 52;         // the slot's NEXT ray, popped ahead by the wave that ran S2: 0 none, 3 pop in flight, 1 held, 2 queues drained
+constexpr int SL_NEXT_RID = 53;
+constexpr int SL_NEXT_REC = 56;           // RayRec, 8 words (16-byte aligned)
+constexpr int SL_CH = 64;                 // coarse: sigma head [128]
+constexpr int SL_CBITS = SL_CH + kMaxSamples;
+constexpr int SL_CWMAX = SL_CBITS + kMaxSamples;
+constexpr int SL_BINS = SL_CWMAX + kMaxSamples;
+constexpr int SL_FH = SL_BINS + kMaxSamples;            // fine: head [4][128]
+constexpr int SL_FBITS = SL_FH + 4 * kMaxSamples;
+constexpr int SL_FWMAX = SL_FBITS + kMaxSamples;
+constexpr int kSlotWords = SL_FWMAX + kMaxSamples;      // 1344 words = 5376 B
+static_assert(kSlotWords % 4 == 0 && SL_REC % 4 == 0 && SL_NEXT_REC % 4 == 0, "slot alignment");
+
+// scratch section of the dynamic LDS (floats): render_kernel's [ray record][Nc + 1 bin edges][4 waves x 32 candidate ids]
+// [RayQueue ints]
+constexpr int SC_SLOT = 0;
+constexpr int SC_BTAB = SC_SLOT + kSlotWords;
+constexpr int SC_CAND = SC_BTAB + (kMaxSamples + 1 + 3) / 4 * 4;
+constexpr int SC_QUEUE = SC_CAND + 4 * 32;
+constexpr int kScratchFloats = SC_QUEUE + (kQueueLdsInts + 3) / 4 * 4;
+static_assert(SC_BTAB % 4 == 0 && SC_QUEUE % 4 == 0 && kScratchFloats % 4 == 0, "16-byte aligned scratch sections");
+template <int MODE>
+__host__ __device__ constexpr int lds_total_floats(int P) {
+    return lds_mlp_floats<MODE>() + 144 + P * kLdsPartStride + P * kLdsCanonStride + kScratchFloats;
+}
 
 
 // host side, defined in enarf_render.hip

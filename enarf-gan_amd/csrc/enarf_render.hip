@@ -648,26 +648,17 @@ __global__ __launch_bounds__(256) void pre_march_kernel(const PreParams q) {
     pack_block<kFeat>(q.tri, q.feat_cl, q.ch_total, q.H, q.W, id % xblocks, (id / xblocks) % q.H, id / (xblocks * q.H), tid, smem);
 }
 
-// scratch layout (floats) of the render kernel; up to kMaxSamples samples per pass
-constexpr int SC_BTAB = 0;        // Nc + 1 bin edges (<= 129)
-constexpr int SC_CAND = 136;      // 4 waves x 32 ints
-constexpr int SC_CH = 264;        // coarse: sigma head [128]
-constexpr int SC_CBITS = 392;     // coarse: bits [128]
-constexpr int SC_CWMAX = 520;     // coarse: wmax [128]
-constexpr int SC_FH = 648;        // fine: head [4][128]
-constexpr int SC_FBITS = 1160;    // fine: bits [128]
-constexpr int SC_FWMAX = 1288;    // fine: wmax [128]
-constexpr int SC_QUEUE = 1416;    // 2 ray ids (current / prefetched)
-constexpr int SC_BINS = 1480;     // importance samples of the ray [128] + 8 skip flags (written by the one wave that runs S2)
-static_assert(SC_QUEUE + kQueueLdsInts <= SC_BINS && SC_BINS + kMaxSamples + 8 <= kScratchFloats, "scratch overflow");
-
 // workgroups of render_kernel per CU = its waves per SIMD (168 VGPRs; measured: 4 spill 71 VGPRs, 0.250 vs 0.224 ms)
 constexpr int kRenderWavesPerSimd = 3;
+static_assert(kRenderWavesPerSimd * 4 * lds_total_floats<ENARF_MLP_F32>(ENARF_MAX_PARTS) <= 160 * 1024 &&
+              kRenderWavesPerSimd * 4 * lds_total_floats<ENARF_MLP_BF16>(ENARF_MAX_PARTS) <= 160 * 1024, "render_kernel's LDS");
 // priority of the one wave that runs S2 while the three others wait at the next barrier for it
 constexpr int kS2Prio = 3;
 
 // SPL = samples per lane in the lane = sample stages: 1 for Nc, Nf <= 64, 2 up to 128 (each wave then loops over two
-// 16-sample tiles per pass)
+// 16-sample tiles per pass). The stages are those of march_kernel (enarf_tasks.h) on ONE ray record in the scratch
+// section; what is this kernel's own is their schedule: which wave takes which tile, which wave runs S2 and S4, the three
+// barriers per ray, the pops and the restaging of the image context.
 template <int MODE, int SPL>
 __global__ __launch_bounds__(256, kRenderWavesPerSimd) void render_kernel(const enarf_render_args a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -675,18 +666,20 @@ __global__ __launch_bounds__(256, kRenderWavesPerSimd) void render_kernel(const 
     // Persistent workgroups: each marches one ray at a time, taken off the (band, cost class) lists the set-up pass
     // filled - heaviest class first chip-wide, own XCD's band first within a class (RayQueue, enarf_march.h).
     const int P = a.P, Nc = a.Nc, Nf = a.Nf, n = a.n;
+    const RenderArgsK ak = kernel_render_args();
     RayQueue rq;
 
     QueryCtx S;
     float *scratch = lds + (lds_total_floats<MODE>(P) - kScratchFloats);
     int *l_q = reinterpret_cast<int *>(scratch + SC_QUEUE);
     float *l_btab = scratch + SC_BTAB;
+    unsigned *sw = reinterpret_cast<unsigned *>(scratch + SC_SLOT);      // the record of the ray being marched
     if (tid <= Nc) l_btab[tid] = linspace_sym(0.0f, 1.0f, Nc + 1, tid);
     __syncthreads();
     // rays without a candidate part first (batches only, enarf_tasks.h): every wave on its own, with a private scratch
     // slot in the not yet staged MLP section of the LDS (4 x 5.4 KB of 28 KB)
     static_assert(4 * kSlotWords <= lds_mlp_floats<MODE>(), "scratch slots of the missed-ray pass");
-    const unsigned n_missed = march_missed_rays<SPL>(kernel_render_args(), l_btab, reinterpret_cast<unsigned *>(lds) + wave * kSlotWords,
+    const unsigned n_missed = march_missed_rays<SPL>(ak, l_btab, reinterpret_cast<unsigned *>(lds) + wave * kSlotWords,
                                                      a.multiply_density_with_weight ? (a.uniform_part_weight ? 2 : 1) : 0, lane);
     if (a.counters && lane == 0 && n_missed) atomicAdd(&a.counters[2], (unsigned long long)n_missed);
     __syncthreads();
@@ -703,16 +696,10 @@ __global__ __launch_bounds__(256, kRenderWavesPerSimd) void render_kernel(const 
     S.H = a.H; S.W = a.W; S.P = P; S.mult_w = a.multiply_density_with_weight ? (a.uniform_part_weight ? 2 : 1) : 0;
     S.clamp_mask = a.clamp_mask; S.uniform_w = a.uniform_part_weight ? 1.0f / (float)P : 0.0f;
     int *l_cand = reinterpret_cast<int *>(scratch + SC_CAND) + wave * 32;
-    float *l_ch = scratch + SC_CH, *l_cwmax = scratch + SC_CWMAX, *l_fh = scratch + SC_FH, *l_fwmax = scratch + SC_FWMAX;
-    uint32_t *l_cbits = reinterpret_cast<uint32_t *>(scratch + SC_CBITS);
-    uint32_t *l_fbits = reinterpret_cast<uint32_t *>(scratch + SC_FBITS);
     __syncthreads();                          // the staged image context is complete before any wave starts a tile
 
-    unsigned n_pairs = 0, n_tiles = 0, n_rays = 0, n_rounds = 0, n_skipped = 0;
+    MarchCounters C{0u, 0u, 0u, 0u, 0u};
     int qslot = 0;
-    const QueryDbg nodbg{nullptr, nullptr, 0, 0};
-    const int j4 = lane >> 2;                              // this lane's sample within the wave's tile
-    const bool dbgq = (a.dbg_fine_density != nullptr);
 
     while (cur >= 0) {
         const uint32_t rid = (uint32_t)cur;
@@ -720,7 +707,7 @@ __global__ __launch_bounds__(256, kRenderWavesPerSimd) void render_kernel(const 
         // one - the atomic's round trip then costs nothing
         const int spare_wave = (3 * SPL * 16 >= Nc) ? ((3 - (int)(rid & 3u)) & 3) : 0;
         if (wave == spare_wave && lane == 0) rq.pop(qslot ^ 1);
-        const int nb = (int)(rid / (uint32_t)n), ray = (int)(rid - (uint32_t)nb * (uint32_t)n);
+        const int nb = (int)(rid / (uint32_t)n);
         if (nb != b) {   // next image: restage its MLP pack and part frames (the lists are in image order, so this is rare)
             b = nb;
             __syncthreads();
@@ -733,246 +720,68 @@ __global__ __launch_bounds__(256, kRenderWavesPerSimd) void render_kernel(const 
         // depth range, candidate parts and ray direction K^-1 [u v w] (rendering.py:26-38): from the set-up pre-pass,
         // left in LDS by the pop
         const RayRec rec = rq.rec(qslot);
-        const float dx = rec.dx, dy = rec.dy, dz = rec.dz;
-        const float dmin = rec.dmin, dmax = rec.dmax;
-        if (wave == 0) n_rays += 1;
+        if (wave == 0) C.rays += 1;
         const int ncand = build_cand_list(l_cand, rec.cand, lane);
-        const float sx = exact_mul(dmin, dx), sy = exact_mul(dmin, dy), sz = exact_mul(dmin, dz);
-        const float ex = exact_mul(dmax, dx), ey = exact_mul(dmax, dy), ez = exact_mul(dmax, dz);
+        const RaySeg seg = ray_segment(rec);
 
-        // ---- S1: coarse pass (rendering.py:119-131, :172) in FULL tiles of 16 bins: tile t of the ray goes to wave slot
-        // t / SPL. With Nc = 48 that is three full tiles instead of four tiles of 12 - a quarter fewer gather rounds
-        // and MLP tiles for the same critical path - and the spared wave rotates ray by ray so that no SIMD idles.
+        // ---- S1: coarse pass in FULL tiles of 16 bins: tile t of the ray goes to wave slot t / SPL. With Nc = 48 that is
+        // three full tiles instead of four tiles of 12 - a quarter fewer gather rounds and MLP tiles for the same critical
+        // path - and the spared wave rotates ray by ray so that no SIMD idles.
         {
             const int slot = (wave + (int)(rid & 3u)) & 3;
 #pragma unroll
             for (int u = 0; u < SPL; ++u) {
-                const int base = (slot * SPL + u) * 16;
-                if (base >= Nc) break;
-                const int i = base + j4;
-                const bool active = i < Nc;
-                const int ci = min(i, Nc - 1);
-                const float b0 = l_btab[ci], b1 = l_btab[ci + 1];
-                const float px = exact_mid(exact_lerp(sx, ex, b1), exact_lerp(sx, ex, b0));
-                const float py = exact_mid(exact_lerp(sy, ey, b1), exact_lerp(sy, ey, b0));
-                const float pz = exact_mid(exact_lerp(sz, ez, b1), exact_lerp(sz, ez, b0));
-                f32x4 o;
-                bool ran;
-                uint32_t bits;
-                float wmax;
-                query_tile<MODE, false>(S, l_cand, ncand, px, py, pz, active, lane, o, ran, bits, wmax, nodbg, n_pairs, n_tiles, &n_rounds);
-                if (lane < 16 && base + lane < Nc) l_ch[base + lane] = o[3];     // MFMA layout: lanes < 16 hold the sample heads
-                if (active && (lane & 3) == 0) { l_cbits[i] = bits; l_cwmax[i] = wmax; }
+                const int t = slot * SPL + u;
+                if (16 * t >= Nc) break;
+                ray_tile<MODE>(a, S, l_btab, l_cand, ncand, sw, seg, false, t, lane, C);
             }
         }
         // the sorted uniforms of the importance draw do not depend on the coarse pass: the wave that will run S2 draws
-        // them now, while the others are still in their coarse tiles (u_(i) = E_1+..+E_i / E_1+..+E_{Nf+1})
+        // them now, while the others are still in their coarse tiles
         float usort[SPL];
 #pragma unroll
         for (int s = 0; s < SPL; ++s) usort[s] = 0.0f;
-        if (wave == spare_wave && !a.bins) {
-            float esum[SPL];
-            uint32_t r1_first = 0;
-#pragma unroll
-            for (int s = 0; s < SPL; ++s) {
-                uint32_t rnd[4];
-                philox4x32((uint32_t)(a.ray_id_base + rid), (uint32_t)((a.ray_id_base + rid) >> 32), (uint32_t)(64 * s + lane), 0x454E4152u, (uint32_t)a.seed, (uint32_t)(a.seed >> 32), rnd);
-                esum[s] = (64 * s + lane < Nf) ? -__logf(1.0f - u32_to_unit(rnd[0])) : 0.0f;
-                if (s == 0) r1_first = rnd[1];
-            }
-            wv_scan_incl<SPL>(esum, lane);
-            const float etot = __shfl(esum[SPL - 1], 63) - __logf(1.0f - u32_to_unit((uint32_t)__shfl((int)r1_first, 0)));
-#pragma unroll
-            for (int s = 0; s < SPL; ++s) usort[s] = fminf(esum[s] / etot, 0.99999994f);
-        }
+        if (wave == spare_wave && !a.bins) draw_sorted_uniforms<SPL>(a, rid, Nf, lane, usort);
         __syncthreads();
         const int next_ray = rq.get(qslot ^ 1);
         qslot ^= 1;
 
-        // ---- S2 (ONE wave, element e = 64 s + lane): weights (rendering.py:180-184), smoothing (:187-190), bins (:192-197).
-        // The result goes through LDS; the other waves wait at the barrier instead of spending the same ~350 VALU
-        // instructions each (the SIMDs are shared with two other workgroups that can use the slots).
-        float *l_bins = scratch + SC_BINS;
-        int *l_skip = reinterpret_cast<int *>(scratch + SC_BINS + kMaxSamples);
+        // ---- S2 on ONE wave: the result goes through LDS; the other waves wait at the barrier instead of spending the
+        // same ~350 VALU instructions each (the SIMDs are shared with two other workgroups that can use the slots).
         if (wave == spare_wave) {
             __builtin_amdgcn_s_setprio(kS2Prio);
-            float bin[SPL];
-            bool skip_tile[4 * SPL];
-
-            float dd[SPL], cs[SPL], T[SPL], wgt[SPL], ws[SPL], wl[SPL], wr[SPL];
-#pragma unroll
-            for (int s = 0; s < SPL; ++s) {
-                const int e = 64 * s + lane;
-                const bool active = e < Nc;
-                const int ci = min(e, Nc - 1);
-                const float den = active ? density_head(l_ch[ci], l_cbits[ci], l_cwmax[ci], S.mult_w, P) : 0.0f;
-                if (a.dbg_coarse_density && active) a.dbg_coarse_density[((size_t)b * n + ray) * Nc + e] = den;
-                const float b0 = l_btab[ci], b1 = l_btab[ci + 1];
-                const float delta = exact_lerp(dmin, dmax, b1) - exact_lerp(dmin, dmax, b0);
-                dd[s] = active ? den * delta * a.render_scale : 0.0f;
-                cs[s] = dd[s];
-            }
-            wv_scan_incl<SPL>(cs, lane);
-#pragma unroll
-            for (int s = 0; s < SPL; ++s) {
-                T[s] = expf(-(cs[s] - dd[s]));
-                wgt[s] = (64 * s + lane < Nc) ? T[s] * (1.0f - expf(-dd[s])) : 0.0f;
-            }
-            wv_prev<SPL>(wgt, wl, lane);
-            wv_next<SPL>(wgt, wr, lane);
-#pragma unroll
-            for (int s = 0; s < SPL; ++s) {
-                const int e = 64 * s + lane;
-                if (e >= Nc - 1) wr[s] = 0.0f;
-                ws[s] = (e < Nc) ? (fmaxf(wl[s], wgt[s]) + fmaxf(wgt[s], wr[s])) / 2.0f + 0.01f : 0.0f;
-            }
-            if (a.bins) {
-#pragma unroll
-                for (int s = 0; s < SPL; ++s) bin[s] = a.bins[((size_t)b * n + ray) * Nf + min(64 * s + lane, Nf - 1)];
-            } else {
-                // Importance samples = Nf iid draws from the piecewise-constant pdf, sorted (rendering.py:192-197).
-                // Sorted uniforms come directly from exponential spacings (u_(i) = E_1+..+E_i / E_1+..+E_{Nf+1}),
-                // each is pushed through the inverse CDF (monotone, so the bins come out sorted): bin index by
-                // binary search, position inside the bin by the leftover - the same law as multinomial + U/Nc.
-                // (the sorted uniforms were drawn before the barrier)
-                float cdf[SPL];
-#pragma unroll
-                for (int s = 0; s < SPL; ++s) cdf[s] = ws[s];
-                wv_scan_incl<SPL>(cdf, lane);
-                const float total = wv_get<SPL>(cdf, Nc - 1);
-#pragma unroll
-                for (int s = 0; s < SPL; ++s) {
-                    const float target = usort[s] * total;
-                    int lo = 0, hi = Nc - 1;   // smallest i with cdf[i] > target
-#pragma unroll
-                    for (int it = 0; it < 5 + SPL; ++it) {
-                        const int mid = (lo + hi) >> 1;
-                        const float c = wv_get<SPL>(cdf, mid);
-                        if (lo < hi) { if (c > target) hi = mid; else lo = mid + 1; }
-                    }
-                    const float c_hi = wv_get<SPL>(cdf, lo), c_lo = wv_get<SPL>(cdf, max(lo - 1, 0));
-                    const float below = (lo > 0) ? c_lo : 0.0f;
-                    const float frac = fminf(fmaxf((target - below) / (c_hi - below), 0.0f), 0.99999994f);
-                    bin[s] = (64 * s + lane < Nf) ? ((float)lo + frac) / (float)Nc : 3.0e38f;
-                }
-            }
-#pragma unroll
-            for (int s = 0; s < SPL; ++s) {
-                l_bins[64 * s + lane] = bin[s];
-                if (a.dbg_bins && 64 * s + lane < Nf) a.dbg_bins[((size_t)b * n + ray) * Nf + 64 * s + lane] = bin[s];
-            }
-            // early ray termination (opt-in, early_stop_eps > 0): transmittance in front of the first fine sample of
-            // each tile, read off the coarse pass (T before coarse bin j). Once it is below eps every sample of the tile
-            // weighs < eps: the tile's gathers and MLP are skipped (its densities count as 0).
-#pragma unroll
-            for (int t = 0; t < 4 * SPL; ++t) {
-                skip_tile[t] = false;
-                if (a.early_stop_eps > 0.0f) {
-                    const float b_first = wv_get<SPL>(bin, min(16 * t, Nf - 1));
-                    const int jbin = min(max((int)(b_first * (float)Nc), 0), Nc - 1);
-                    skip_tile[t] = wv_get<SPL>(T, jbin) < a.early_stop_eps;
-                }
-                if (lane == 0) l_skip[t] = skip_tile[t] ? 1 : 0;
-            }
+            ray_sample_stage<SPL>(a, l_btab, sw, rid, rec.dmin, rec.dmax, usort, S.mult_w, lane);
             __builtin_amdgcn_s_setprio(0);
         }
         __syncthreads();
 
-        // ---- S3: fine pass, in full tiles of 16 samples like the coarse pass (tile T on wave slot T / SPL; Nf = 48 or 32
-        // leave one or two waves without a tile); the last sample only closes the last interval and is never queried
+        // ---- S3: fine pass, in full tiles of 16 samples like the coarse pass (tile t on wave slot t / SPL; Nf = 48 or 32
+        // leave one or two waves without a tile)
         {
             const int slotf = (wave + (int)((rid >> 2) & 3u)) & 3;
 #pragma unroll
             for (int u = 0; u < SPL; ++u) {
-                const int T = slotf * SPL + u, base = T * 16;
-                if (base >= Nf) break;
-                const int i = base + j4;
-                const bool skip = l_skip[T] != 0;
-                const bool active = (i < (dbgq ? Nf : Nf - 1)) && !skip;
-                const float bi = l_bins[min(i, Nf - 1)];
-                const float px = exact_lerp(sx, ex, bi), py = exact_lerp(sy, ey, bi), pz = exact_lerp(sz, ez, bi);
-                f32x4 o;
-                bool ran;
-                uint32_t bits;
-                float wmax;
-                query_tile<MODE, false>(S, l_cand, ncand, px, py, pz, active, lane, o, ran, bits, wmax, nodbg, n_pairs, n_tiles, &n_rounds);
-                if (lane < 16 && base + lane < Nf) {
-                    const int io = base + lane;
-                    l_fh[io] = o[0]; l_fh[kMaxSamples + io] = o[1]; l_fh[2 * kMaxSamples + io] = o[2]; l_fh[3 * kMaxSamples + io] = o[3];
-                }
-                if (i < Nf && (lane & 3) == 0) { l_fbits[i] = active ? bits : 0u; l_fwmax[i] = wmax; }
-                if (skip && lane == 0) n_skipped += 1;
+                const int t = slotf * SPL + u;
+                if (16 * t >= Nf) break;
+                ray_tile<MODE>(a, S, l_btab, l_cand, ncand, sw, seg, true, t, lane, C);
             }
         }
         __syncthreads();
 
-        // ---- S4 (one wave, element e = 64 s + lane): compositing (rendering.py:307-335). It runs while the other waves are
-        // already in the next ray's coarse pass - on the wave that has no coarse tile there, when there is one.
+        // ---- S4 on one wave, while the other waves are already in the next ray's coarse pass - on the wave that has no
+        // coarse tile there, when there is one.
         const int s4_wave = (next_ray >= 0 && 3 * SPL * 16 >= Nc) ? ((3 - (next_ray & 3)) & 3) : 0;
-        if (wave == s4_wave) {
-            float fdepth[SPL], dnext[SPL], den[SPL], cr[SPL], cg[SPL], cb[SPL], dd[SPL], cs[SPL];
-#pragma unroll
-            for (int s = 0; s < SPL; ++s) {
-                const int e = 64 * s + lane;
-                const int ci = min(e, Nf - 1);
-                const bool have = e < (dbgq ? Nf : Nf - 1);
-                const uint32_t bits = l_fbits[ci];
-                den[s] = have ? density_head(l_fh[3 * kMaxSamples + ci], bits, l_fwmax[ci], S.mult_w, P) : 0.0f;
-                cr[s] = tanhf(l_fh[ci]); cg[s] = tanhf(l_fh[kMaxSamples + ci]); cb[s] = tanhf(l_fh[2 * kMaxSamples + ci]);
-                fdepth[s] = exact_lerp(dmin, dmax, l_bins[64 * s + lane]);
-                if (dbgq && e < Nf) {
-                    const size_t o = ((size_t)b * n + ray) * Nf + e;
-                    a.dbg_fine_density[o] = den[s];
-                    if (a.dbg_fine_valid) a.dbg_fine_valid[o] = bits;
-                    if (a.dbg_fine_color) {
-                        a.dbg_fine_color[(((size_t)b * 3 + 0) * n + ray) * Nf + e] = cr[s];
-                        a.dbg_fine_color[(((size_t)b * 3 + 1) * n + ray) * Nf + e] = cg[s];
-                        a.dbg_fine_color[(((size_t)b * 3 + 2) * n + ray) * Nf + e] = cb[s];
-                    }
-                }
-            }
-            wv_next<SPL>(fdepth, dnext, lane);
-#pragma unroll
-            for (int s = 0; s < SPL; ++s) {
-                dd[s] = (64 * s + lane < Nf - 1) ? den[s] * (dnext[s] - fdepth[s]) * a.render_scale : 0.0f;
-                cs[s] = dd[s];
-            }
-            wv_scan_incl<SPL>(cs, lane);
-            float wgt[SPL], vr[SPL], vg[SPL], vb[SPL], vd[SPL];
-#pragma unroll
-            for (int s = 0; s < SPL; ++s) {
-                const bool seg = 64 * s + lane < Nf - 1;
-                const float T = expf(-(cs[s] - dd[s]));
-                wgt[s] = seg ? T * (1.0f - expf(-dd[s])) : 0.0f;
-                vr[s] = wgt[s] * cr[s]; vg[s] = wgt[s] * cg[s]; vb[s] = wgt[s] * cb[s];
-                vd[s] = seg ? (wgt[s] * 1.0f) / fdepth[s] : 0.0f;
-            }
-            const float o_r = wv_sum<SPL>(vr), o_g = wv_sum<SPL>(vg), o_b = wv_sum<SPL>(vb);
-            const float o_m = wv_sum<SPL>(wgt), o_d = wv_sum<SPL>(vd);
-            if (lane == 0) {
-                a.color[((size_t)b * 3 + 0) * n + ray] = o_r;
-                a.color[((size_t)b * 3 + 1) * n + ray] = o_g;
-                a.color[((size_t)b * 3 + 2) * n + ray] = o_b;
-                a.mask[(size_t)b * n + ray] = o_m;
-                a.disparity[(size_t)b * n + ray] = o_d;
-            }
-#pragma unroll
-            for (int s = 0; s < SPL; ++s) {
-                const int e = 64 * s + lane;
-                if (a.fine_weights && e < Nf - 1) a.fine_weights[((size_t)b * n + ray) * (Nf - 1) + e] = wgt[s];
-                if (a.fine_depth && e < Nf) a.fine_depth[((size_t)b * n + ray) * Nf + e] = fdepth[s];
-            }
-        }
+        if (wave == s4_wave) ray_composite_stage<SPL>(a, sw, rid, rec.dmin, rec.dmax, S.mult_w, lane);
         // no barrier needed here: coarse arrays are rewritten in S1' (after this ray's S3 barrier, which follows every
         // wave's S2 reads), fine arrays in S3' (after the S1' barrier, which wave 0 reaches only after this S4).
         cur = next_ray;
     }
     if (a.counters && lane == 0) {
-        atomicAdd(&a.counters[0], (unsigned long long)n_pairs);
-        atomicAdd(&a.counters[1], (unsigned long long)n_tiles);
-        atomicAdd(&a.counters[2], (unsigned long long)n_rays);
-        atomicAdd(&a.counters[3], (unsigned long long)n_rounds);
-        atomicAdd(&a.counters[4], (unsigned long long)n_skipped);
+        atomicAdd(&a.counters[0], (unsigned long long)C.pairs);
+        atomicAdd(&a.counters[1], (unsigned long long)C.tiles);
+        atomicAdd(&a.counters[2], (unsigned long long)C.rays);
+        atomicAdd(&a.counters[3], (unsigned long long)C.rounds);
+        atomicAdd(&a.counters[4], (unsigned long long)C.skipped);
     }
 }
 
@@ -1106,7 +915,8 @@ int device_cus() {
 }
 }  // namespace enarf
 
-// Two march kernels share every stage (enarf_march.h, enarf_query.h, enarf_tasks.h) and produce the same bits:
+// Two march kernels run the same stage code (the tiles, S2 and S4 of enarf_tasks.h on a per-ray record in the slot layout of
+// enarf_march.h) and differ only in how they schedule it, so they produce the same bits:
 //   render_kernel   one workgroup (4 waves) marches one ray at a time, 3 workgroups per CU, three barriers per ray;
 //   march_kernel    one workgroup (12 waves) per CU, several rays in flight, 16-sample tiles claimed as tasks.
 // enarf_render_args.march picks one; ENARF_MARCH_AUTO picks by shape, from measurements on MI355X: the

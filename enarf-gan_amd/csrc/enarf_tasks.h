@@ -1,6 +1,12 @@
-// enarf_tasks.h - the ray march as a pool of tile tasks (round 2; the second march kernel beside the barrier-structured
-// workgroup-per-ray render_kernel of enarf_render.hip - same stages, same bits; enarf_render_args.march picks one), the
-// two serial ray stages both kernels share, and the pass over the rays that miss every cube.
+// enarf_tasks.h - the stages of the forward march, the kernel that runs them as a pool of tile tasks (march_kernel, round 2)
+// and the pass over the rays that miss every cube. Both march kernels run ONE definition of each stage, on a per-ray LDS
+// record in the slot layout (SL_*, enarf_march.h):
+//   S1, S3  ray_tile              one 16-sample tile of the coarse / fine pass: positions, query_tile, heads / bits / wmax
+//   S2      ray_sample_stage      coarse weights, smoothing, importance samples (bins_from_cdf of the uniforms that
+//                                 draw_sorted_uniforms drew), early-termination flags
+//   S4      ray_composite_stage   compositing and the ray's outputs
+// They differ only in the schedule: render_kernel (enarf_render.hip) marches one ray per 4-wave workgroup behind three
+// barriers; march_kernel, below, keeps several rays in flight. Same stages, same bits; enarf_render_args.march picks one.
 //
 // One persistent workgroup of NW wavefronts per CU keeps R rays in flight, each in an LDS "slot". A ray's life is a chain
 //     pop -> C coarse tiles -> S2 (weights, importance samples) -> F fine tiles -> S4 (compositing, outputs) -> pop ...
@@ -26,29 +32,6 @@
 #include "enarf_march.h"
 
 namespace enarf {
-
-constexpr int kMaxSamples = 128;          // samples per pass (two per lane in the lane = sample stages above 64)
-
-// ---- LDS slot of one ray in flight (32-bit words) ---------------------------------------------------------------------
-constexpr int SL_CTL = 0;                 // control word, see pack_ctl
-constexpr int SL_DONE = 1;                // completed tiles of the current stage
-constexpr int SL_RID = 2;                 // global ray id (image * n + ray)
-constexpr int SL_NCAND = 3;
-constexpr int SL_REC = 4;                 // RayRec, 8 words (16-byte aligned)
-constexpr int SL_CAND = 12;               // candidate part ids, 32 ints
-constexpr int SL_SKIP = 44;               // early-termination flags per fine tile, 8 ints
-constexpr int SL_NEXT_STATE = 52;         // the slot's NEXT ray, popped ahead by the wave that ran S2: 0 none, 3 pop in flight, 1 held, 2 queues drained
-constexpr int SL_NEXT_RID = 53;
-constexpr int SL_NEXT_REC = 56;           // RayRec, 8 words (16-byte aligned)
-constexpr int SL_CH = 64;                 // coarse: sigma head [128]
-constexpr int SL_CBITS = SL_CH + kMaxSamples;
-constexpr int SL_CWMAX = SL_CBITS + kMaxSamples;
-constexpr int SL_BINS = SL_CWMAX + kMaxSamples;
-constexpr int SL_FH = SL_BINS + kMaxSamples;            // fine: head [4][128]
-constexpr int SL_FBITS = SL_FH + 4 * kMaxSamples;
-constexpr int SL_FWMAX = SL_FBITS + kMaxSamples;
-constexpr int kSlotWords = SL_FWMAX + kMaxSamples;      // 1344 words = 5376 B
-static_assert(kSlotWords % 4 == 0 && SL_REC % 4 == 0 && SL_NEXT_REC % 4 == 0, "slot alignment");
 
 // stages of the control word
 constexpr unsigned ST_NONE = 0, ST_COARSE = 1, ST_FINE = 2;
@@ -161,6 +144,10 @@ typedef const __attribute__((address_space(4))) enarf_render_args *RenderArgsK;
 __device__ __forceinline__ RenderArgsK kernel_render_args() {
     return (RenderArgsK)__builtin_amdgcn_kernarg_segment_ptr();
 }
+// The shared stages take a plain reference: render_kernel inlines them on its own argument, whose fields the compiler then
+// loads once per launch instead of once per ray; the out-of-line callers pass this one (the address space cast folds
+// away, the loads stay scalar loads of the kernarg segment).
+__device__ __forceinline__ const enarf_render_args &render_args_ref(RenderArgsK a) { return *(const enarf_render_args *)a; }
 
 // everything a task needs that is the same for the whole launch / workgroup
 struct MarchCtx {
@@ -174,14 +161,14 @@ struct MarchCtx {
 struct MarchCounters { unsigned pairs, tiles, rays, rounds, skipped; };
 
 template <int SPL>
-__device__ __forceinline__ void draw_sorted_uniforms(RenderArgsK a, uint32_t rid, int Nf, int lane, float usort[SPL]) {
+__device__ __forceinline__ void draw_sorted_uniforms(const enarf_render_args &a, uint32_t rid, int Nf, int lane, float usort[SPL]) {
     // u_(i) = (E_1 + .. + E_i) / (E_1 + .. + E_{Nf+1}): sorted uniforms from exponential spacings (Philox4x32-10)
     float esum[SPL];
     uint32_t r1_first = 0;
 #pragma unroll
     for (int s = 0; s < SPL; ++s) {
         uint32_t rnd[4];
-        philox4x32((uint32_t)(a->ray_id_base + rid), (uint32_t)((a->ray_id_base + rid) >> 32), (uint32_t)(64 * s + lane), 0x454E4152u, (uint32_t)a->seed, (uint32_t)(a->seed >> 32), rnd);
+        philox4x32((uint32_t)(a.ray_id_base + rid), (uint32_t)((a.ray_id_base + rid) >> 32), (uint32_t)(64 * s + lane), 0x454E4152u, (uint32_t)a.seed, (uint32_t)(a.seed >> 32), rnd);
         esum[s] = (64 * s + lane < Nf) ? -__logf(1.0f - u32_to_unit(rnd[0])) : 0.0f;
         if (s == 0) r1_first = rnd[1];
     }
@@ -191,11 +178,10 @@ __device__ __forceinline__ void draw_sorted_uniforms(RenderArgsK a, uint32_t rid
     for (int s = 0; s < SPL; ++s) usort[s] = fminf(esum[s] / etot, 0.99999994f);
 }
 
-// Nf sorted importance samples of ray `rid` from the (inclusive, unnormalised) cdf of its Nc smoothed coarse weights
+// the inverse-CDF step: Nf sorted importance samples from the (inclusive, unnormalised) cdf of Nc smoothed coarse weights
+// and Nf sorted uniforms (draw_sorted_uniforms)
 template <int SPL>
-__device__ __forceinline__ void bins_from_cdf(RenderArgsK a, uint32_t rid, int Nc, int Nf, const float cdf[SPL], int lane, float bin[SPL]) {
-    float usort[SPL];
-    draw_sorted_uniforms<SPL>(a, rid, Nf, lane, usort);
+__device__ __forceinline__ void bins_from_cdf(int Nc, int Nf, const float cdf[SPL], const float usort[SPL], int lane, float bin[SPL]) {
     const float total = wv_get<SPL>(cdf, Nc - 1);
 #pragma unroll
     for (int s = 0; s < SPL; ++s) {
@@ -214,15 +200,14 @@ __device__ __forceinline__ void bins_from_cdf(RenderArgsK a, uint32_t rid, int N
     }
 }
 
-// S2 of one ray (ONE wave, element e = 64 s + lane): coarse weights (rendering.py:180-184), smoothing (:187-190), the
-// importance samples (:192-197) and the early-termination flags of the fine tiles; everything from / to the slot
+// S2 of ray `rid` (ONE wave, element e = 64 s + lane): coarse weights (rendering.py:180-184), smoothing (:187-190), the
+// importance samples (:192-197) and the early-termination flags of the fine tiles. `usort`: the ray's sorted uniforms
+// (draw_sorted_uniforms; not read when a.bins is given). Heads in, bins and flags out: the ray's record `sw`.
 template <int SPL>
-__device__ __noinline__ void ray_sample_stage(RenderArgsK a, const float *l_btab, unsigned *sw, int mult_w, int lane) {
-    const int P = a->P, Nc = a->Nc, Nf = a->Nf, n = a->n;
-    const RayRec rec = *reinterpret_cast<const RayRec *>(sw + SL_REC);
-    const uint32_t rid = sw[SL_RID];
+__device__ __forceinline__ void ray_sample_stage(const enarf_render_args &a, const float *l_btab, unsigned *sw, uint32_t rid,
+                                                 float dmin, float dmax, const float usort[SPL], int mult_w, int lane) {
+    const int P = a.P, Nc = a.Nc, Nf = a.Nf, n = a.n;
     const int b = (int)(rid / (uint32_t)n), ray = (int)(rid - (uint32_t)b * (uint32_t)n);
-    const float dmin = rec.dmin, dmax = rec.dmax;
     const float *l_ch = reinterpret_cast<const float *>(sw + SL_CH), *l_cwmax = reinterpret_cast<const float *>(sw + SL_CWMAX);
     const uint32_t *l_cbits = sw + SL_CBITS;
     float *l_bins = reinterpret_cast<float *>(sw + SL_BINS);
@@ -235,10 +220,10 @@ __device__ __noinline__ void ray_sample_stage(RenderArgsK a, const float *l_btab
         const bool active = e < Nc;
         const int ci = min(e, Nc - 1);
         const float den = active ? density_head(l_ch[ci], l_cbits[ci], l_cwmax[ci], mult_w, P) : 0.0f;
-        if (a->dbg_coarse_density && active) a->dbg_coarse_density[((size_t)b * n + ray) * Nc + e] = den;
+        if (a.dbg_coarse_density && active) a.dbg_coarse_density[((size_t)b * n + ray) * Nc + e] = den;
         const float b0 = l_btab[ci], b1 = l_btab[ci + 1];
         const float delta = exact_lerp(dmin, dmax, b1) - exact_lerp(dmin, dmax, b0);
-        dd[s] = active ? den * delta * a->render_scale : 0.0f;
+        dd[s] = active ? den * delta * a.render_scale : 0.0f;
         cs[s] = dd[s];
     }
     wv_scan_incl<SPL>(cs, lane);
@@ -255,9 +240,9 @@ __device__ __noinline__ void ray_sample_stage(RenderArgsK a, const float *l_btab
         if (e >= Nc - 1) wr[s] = 0.0f;
         ws[s] = (e < Nc) ? (fmaxf(wl[s], wgt[s]) + fmaxf(wgt[s], wr[s])) / 2.0f + 0.01f : 0.0f;
     }
-    if (a->bins) {
+    if (a.bins) {
 #pragma unroll
-        for (int s = 0; s < SPL; ++s) bin[s] = a->bins[((size_t)b * n + ray) * Nf + min(64 * s + lane, Nf - 1)];
+        for (int s = 0; s < SPL; ++s) bin[s] = a.bins[((size_t)b * n + ray) * Nf + min(64 * s + lane, Nf - 1)];
     } else {
         // Importance samples = Nf iid draws from the piecewise-constant pdf, sorted (rendering.py:192-197): sorted uniforms
         // pushed through the inverse CDF (monotone, so the bins come out sorted) - bin index by binary search, position
@@ -266,39 +251,49 @@ __device__ __noinline__ void ray_sample_stage(RenderArgsK a, const float *l_btab
 #pragma unroll
         for (int s = 0; s < SPL; ++s) cdf[s] = ws[s];
         wv_scan_incl<SPL>(cdf, lane);
-        bins_from_cdf<SPL>(a, rid, Nc, Nf, cdf, lane, bin);
+        bins_from_cdf<SPL>(Nc, Nf, cdf, usort, lane, bin);
     }
 #pragma unroll
     for (int s = 0; s < SPL; ++s) {
         l_bins[64 * s + lane] = bin[s];
-        if (a->dbg_bins && 64 * s + lane < Nf) a->dbg_bins[((size_t)b * n + ray) * Nf + 64 * s + lane] = bin[s];
+        if (a.dbg_bins && 64 * s + lane < Nf) a.dbg_bins[((size_t)b * n + ray) * Nf + 64 * s + lane] = bin[s];
     }
     // early ray termination (opt-in, early_stop_eps > 0): transmittance in front of the first fine sample of each tile,
     // read off the coarse pass. Below eps every sample of the tile weighs < eps: the tile is skipped (densities 0).
 #pragma unroll
     for (int t = 0; t < 4 * SPL; ++t) {
         bool skip = false;
-        if (a->early_stop_eps > 0.0f) {
+        if (a.early_stop_eps > 0.0f) {
             const float b_first = wv_get<SPL>(bin, min(16 * t, Nf - 1));
             const int jbin = min(max((int)(b_first * (float)Nc), 0), Nc - 1);
-            skip = wv_get<SPL>(T, jbin) < a->early_stop_eps;
+            skip = wv_get<SPL>(T, jbin) < a.early_stop_eps;
         }
         if (lane == 0) l_skip[t] = skip ? 1 : 0;
     }
 }
 
-// S4 of one ray (ONE wave, element e = 64 s + lane): compositing (rendering.py:307-335) and the ray's outputs
+// S2 of the ray a record holds (march_kernel, the missed-ray pass)
 template <int SPL>
-__device__ __noinline__ void ray_composite_stage(RenderArgsK a, unsigned *sw, int mult_w, int lane) {
-    const int P = a->P, Nf = a->Nf, n = a->n;
+__device__ __noinline__ void slot_sample_stage(RenderArgsK ak, const float *l_btab, unsigned *sw, int mult_w, int lane) {
+    const enarf_render_args &a = render_args_ref(ak);
     const RayRec rec = *reinterpret_cast<const RayRec *>(sw + SL_REC);
     const uint32_t rid = sw[SL_RID];
+    float usort[SPL] = {};
+    if (!a.bins) draw_sorted_uniforms<SPL>(a, rid, a.Nf, lane, usort);
+    ray_sample_stage<SPL>(a, l_btab, sw, rid, rec.dmin, rec.dmax, usort, mult_w, lane);
+}
+
+// S4 of ray `rid` (ONE wave, element e = 64 s + lane): compositing (rendering.py:307-335) and the ray's outputs, from the
+// fine heads and bins of its record `sw`
+template <int SPL>
+__device__ __forceinline__ void ray_composite_stage(const enarf_render_args &a, const unsigned *sw, uint32_t rid, float dmin,
+                                                    float dmax, int mult_w, int lane) {
+    const int P = a.P, Nf = a.Nf, n = a.n;
     const int b = (int)(rid / (uint32_t)n), ray = (int)(rid - (uint32_t)b * (uint32_t)n);
-    const float dmin = rec.dmin, dmax = rec.dmax;
     const float *l_fh = reinterpret_cast<const float *>(sw + SL_FH), *l_fwmax = reinterpret_cast<const float *>(sw + SL_FWMAX);
     const float *l_bins = reinterpret_cast<const float *>(sw + SL_BINS);
     const uint32_t *l_fbits = sw + SL_FBITS;
-    const bool dbgq = (a->dbg_fine_density != nullptr);
+    const bool dbgq = (a.dbg_fine_density != nullptr);
     float fdepth[SPL], dnext[SPL], den[SPL], cr[SPL], cg[SPL], cb[SPL], dd[SPL], cs[SPL];
 #pragma unroll
     for (int s = 0; s < SPL; ++s) {
@@ -311,19 +306,19 @@ __device__ __noinline__ void ray_composite_stage(RenderArgsK a, unsigned *sw, in
         fdepth[s] = exact_lerp(dmin, dmax, l_bins[64 * s + lane]);
         if (dbgq && e < Nf) {
             const size_t o = ((size_t)b * n + ray) * Nf + e;
-            a->dbg_fine_density[o] = den[s];
-            if (a->dbg_fine_valid) a->dbg_fine_valid[o] = bits;
-            if (a->dbg_fine_color) {
-                a->dbg_fine_color[(((size_t)b * 3 + 0) * n + ray) * Nf + e] = cr[s];
-                a->dbg_fine_color[(((size_t)b * 3 + 1) * n + ray) * Nf + e] = cg[s];
-                a->dbg_fine_color[(((size_t)b * 3 + 2) * n + ray) * Nf + e] = cb[s];
+            a.dbg_fine_density[o] = den[s];
+            if (a.dbg_fine_valid) a.dbg_fine_valid[o] = bits;
+            if (a.dbg_fine_color) {
+                a.dbg_fine_color[(((size_t)b * 3 + 0) * n + ray) * Nf + e] = cr[s];
+                a.dbg_fine_color[(((size_t)b * 3 + 1) * n + ray) * Nf + e] = cg[s];
+                a.dbg_fine_color[(((size_t)b * 3 + 2) * n + ray) * Nf + e] = cb[s];
             }
         }
     }
     wv_next<SPL>(fdepth, dnext, lane);
 #pragma unroll
     for (int s = 0; s < SPL; ++s) {
-        dd[s] = (64 * s + lane < Nf - 1) ? den[s] * (dnext[s] - fdepth[s]) * a->render_scale : 0.0f;
+        dd[s] = (64 * s + lane < Nf - 1) ? den[s] * (dnext[s] - fdepth[s]) * a.render_scale : 0.0f;
         cs[s] = dd[s];
     }
     wv_scan_incl<SPL>(cs, lane);
@@ -339,36 +334,41 @@ __device__ __noinline__ void ray_composite_stage(RenderArgsK a, unsigned *sw, in
     const float o_r = wv_sum<SPL>(vr), o_g = wv_sum<SPL>(vg), o_b = wv_sum<SPL>(vb);
     const float o_m = wv_sum<SPL>(wgt), o_d = wv_sum<SPL>(vd);
     if (lane == 0) {
-        a->color[((size_t)b * 3 + 0) * n + ray] = o_r;
-        a->color[((size_t)b * 3 + 1) * n + ray] = o_g;
-        a->color[((size_t)b * 3 + 2) * n + ray] = o_b;
-        a->mask[(size_t)b * n + ray] = o_m;
-        a->disparity[(size_t)b * n + ray] = o_d;
+        a.color[((size_t)b * 3 + 0) * n + ray] = o_r;
+        a.color[((size_t)b * 3 + 1) * n + ray] = o_g;
+        a.color[((size_t)b * 3 + 2) * n + ray] = o_b;
+        a.mask[(size_t)b * n + ray] = o_m;
+        a.disparity[(size_t)b * n + ray] = o_d;
     }
 #pragma unroll
     for (int s = 0; s < SPL; ++s) {
         const int e = 64 * s + lane;
-        if (a->fine_weights && e < Nf - 1) a->fine_weights[((size_t)b * n + ray) * (Nf - 1) + e] = wgt[s];
-        if (a->fine_depth && e < Nf) a->fine_depth[((size_t)b * n + ray) * Nf + e] = fdepth[s];
+        if (a.fine_weights && e < Nf - 1) a.fine_weights[((size_t)b * n + ray) * (Nf - 1) + e] = wgt[s];
+        if (a.fine_depth && e < Nf) a.fine_depth[((size_t)b * n + ray) * Nf + e] = fdepth[s];
     }
 }
 
-// one 16-sample query tile of a ray: coarse tile t (bin mid-points, rendering.py:119-131) or fine tile t (the ray's
-// importance samples); results go to the slot. ONE call site of query_tile for both passes.
-template <int MODE>
-__device__ __forceinline__ void ray_tile_task(const enarf_render_args &a, const MarchCtx &M, QueryCtx &S, unsigned *sw, bool fine,
-                                              int t, int lane, MarchCounters &C) {
-    const int Nc = a.Nc, Nf = a.Nf, n = a.n;
+// S4 of the ray a record holds (march_kernel, the missed-ray pass)
+template <int SPL>
+__device__ __noinline__ void slot_composite_stage(RenderArgsK ak, unsigned *sw, int mult_w, int lane) {
     const RayRec rec = *reinterpret_cast<const RayRec *>(sw + SL_REC);
-    const uint32_t rid = (uint32_t)__builtin_amdgcn_readfirstlane((int)sw[SL_RID]);      // wave-uniform: plane bases in SGPRs
-    const int b = (int)(rid / (uint32_t)n);
-    S.feat = a.feat_cl + (size_t)b * a.feat_batch_stride;
-    S.mask = a.mask_planes + (size_t)b * a.mask_batch_stride;
-    const int ncand = (int)sw[SL_NCAND];
-    const int *l_cand = reinterpret_cast<const int *>(sw + SL_CAND);
-    const float dmin = rec.dmin, dmax = rec.dmax;
-    const float sx = exact_mul(dmin, rec.dx), sy = exact_mul(dmin, rec.dy), sz = exact_mul(dmin, rec.dz);
-    const float ex = exact_mul(dmax, rec.dx), ey = exact_mul(dmax, rec.dy), ez = exact_mul(dmax, rec.dz);
+    ray_composite_stage<SPL>(render_args_ref(ak), sw, sw[SL_RID], rec.dmin, rec.dmax, mult_w, lane);
+}
+
+// the ray's points at depth dmin and dmax: every sample position is interpolated between them
+struct RaySeg { float sx, sy, sz, ex, ey, ez; };
+__device__ __forceinline__ RaySeg ray_segment(const RayRec &rec) {
+    return {exact_mul(rec.dmin, rec.dx), exact_mul(rec.dmin, rec.dy), exact_mul(rec.dmin, rec.dz),
+            exact_mul(rec.dmax, rec.dx), exact_mul(rec.dmax, rec.dy), exact_mul(rec.dmax, rec.dz)};
+}
+
+// one 16-sample query tile of a ray: coarse tile t (bin mid-points, rendering.py:119-131) or fine tile t (the ray's
+// importance samples, from its record); results go to the ray's record `sw`. ONE call site of query_tile for both passes
+// and both march kernels.
+template <int MODE>
+__device__ __forceinline__ void ray_tile(const enarf_render_args &a, const QueryCtx &S, const float *l_btab, const int *l_cand,
+                                         int ncand, unsigned *sw, const RaySeg &g, bool fine, int t, int lane, MarchCounters &C) {
+    const int Nc = a.Nc, Nf = a.Nf;
     const int j4 = lane >> 2, base = 16 * t, i = base + j4;
     const int N = fine ? Nf : Nc;                                  // samples of this pass
     const bool dbgq = (a.dbg_fine_density != nullptr);
@@ -377,15 +377,15 @@ __device__ __forceinline__ void ray_tile_task(const enarf_render_args &a, const 
     if (!fine) {       // wave-uniform
         active = i < Nc;
         const int ci = min(i, Nc - 1);
-        const float b0 = M.btab[ci], b1 = M.btab[ci + 1];
-        px = exact_mid(exact_lerp(sx, ex, b1), exact_lerp(sx, ex, b0));
-        py = exact_mid(exact_lerp(sy, ey, b1), exact_lerp(sy, ey, b0));
-        pz = exact_mid(exact_lerp(sz, ez, b1), exact_lerp(sz, ez, b0));
+        const float b0 = l_btab[ci], b1 = l_btab[ci + 1];
+        px = exact_mid(exact_lerp(g.sx, g.ex, b1), exact_lerp(g.sx, g.ex, b0));
+        py = exact_mid(exact_lerp(g.sy, g.ey, b1), exact_lerp(g.sy, g.ey, b0));
+        pz = exact_mid(exact_lerp(g.sz, g.ez, b1), exact_lerp(g.sz, g.ez, b0));
     } else {
         skip = reinterpret_cast<const int *>(sw + SL_SKIP)[t] != 0;
         active = (i < (dbgq ? Nf : Nf - 1)) && !skip;              // the last sample only closes the last interval
         const float bi = reinterpret_cast<const float *>(sw + SL_BINS)[min(i, Nf - 1)];
-        px = exact_lerp(sx, ex, bi); py = exact_lerp(sy, ey, bi); pz = exact_lerp(sz, ez, bi);
+        px = exact_lerp(g.sx, g.ex, bi); py = exact_lerp(g.sy, g.ey, bi); pz = exact_lerp(g.sz, g.ez, bi);
     }
     const QueryDbg nodbg{nullptr, nullptr, 0, 0};
     f32x4 o;
@@ -405,6 +405,19 @@ __device__ __forceinline__ void ray_tile_task(const enarf_render_args &a, const 
         reinterpret_cast<float *>(sw + (fine ? SL_FWMAX : SL_CWMAX))[i] = wmax;
     }
     if (skip) C.skipped += 1;
+}
+
+// tile t of the ray in slot `sw` (march_kernel): the plane bases of its image, its candidates and segment from the slot
+template <int MODE>
+__device__ __forceinline__ void ray_tile_task(const enarf_render_args &a, const MarchCtx &M, QueryCtx &S, unsigned *sw, bool fine,
+                                              int t, int lane, MarchCounters &C) {
+    const RayRec rec = *reinterpret_cast<const RayRec *>(sw + SL_REC);
+    const uint32_t rid = (uint32_t)__builtin_amdgcn_readfirstlane((int)sw[SL_RID]);      // wave-uniform: plane bases in SGPRs
+    const int b = (int)(rid / (uint32_t)a.n);
+    S.feat = a.feat_cl + (size_t)b * a.feat_batch_stride;
+    S.mask = a.mask_planes + (size_t)b * a.mask_batch_stride;
+    ray_tile<MODE>(a, S, M.btab, reinterpret_cast<const int *>(sw + SL_CAND), (int)sw[SL_NCAND], sw, ray_segment(rec), fine, t,
+                   lane, C);
 }
 
 // ---- rays that miss every cube (batches only; a single image drops them in the set-up pass) --------------------------
@@ -427,7 +440,9 @@ __device__ __forceinline__ void missed_ray_short_cut(RenderArgsK a, uint32_t rid
 #pragma unroll
         for (int s = 0; s < SPL; ++s) bin[s] = a->bins[((size_t)b * n + ray) * Nf + min(64 * s + lane, Nf - 1)];
     } else {
-        bins_from_cdf<SPL>(a, rid, Nc, Nf, cdf, lane, bin);
+        float usort[SPL];
+        draw_sorted_uniforms<SPL>(render_args_ref(a), rid, Nf, lane, usort);
+        bins_from_cdf<SPL>(Nc, Nf, cdf, usort, lane, bin);
     }
     if (lane < 3) a->color[((size_t)b * 3 + lane) * n + ray] = 0.0f;
     if (lane == 3) a->mask[(size_t)b * n + ray] = 0.0f;
@@ -483,8 +498,8 @@ __device__ __forceinline__ unsigned march_missed_rays(RenderArgsK ak, const floa
                         scratch[SL_RID] = rid;
                         *reinterpret_cast<RayRec *>(scratch + SL_REC) = recs[rid];
                     }
-                    ray_sample_stage<SPL>(ak, l_btab, scratch, mult_w, lane);
-                    ray_composite_stage<SPL>(ak, scratch, mult_w, lane);
+                    slot_sample_stage<SPL>(ak, l_btab, scratch, mult_w, lane);
+                    slot_composite_stage<SPL>(ak, scratch, mult_w, lane);
                 } else {
                     missed_ray_short_cut<SPL>(ak, rid, recs[rid], cdf, lane);
                 }
@@ -728,7 +743,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void march_kernel(const enarf_rend
                 lds_acquire();
                 if (!fine) {
                     __builtin_amdgcn_s_setprio(3);   // fine tiles of this ray cannot start before this is done
-                    ray_sample_stage<SPL>(ak, M.btab, sw, S.mult_w, lane);
+                    slot_sample_stage<SPL>(ak, M.btab, sw, S.mult_w, lane);
                     __builtin_amdgcn_s_setprio(0);
                     if (lane == 0) sw[SL_DONE] = 0u;
                     lds_release();
@@ -740,7 +755,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void march_kernel(const enarf_rend
                     __builtin_amdgcn_s_setprio(0);
                 } else {
                     __builtin_amdgcn_s_setprio(3);   // the slot is empty until this chain has published its next ray
-                    ray_composite_stage<SPL>(ak, sw, S.mult_w, lane);
+                    slot_composite_stage<SPL>(ak, sw, S.mult_w, lane);
                     C.rays += refill_slot<MODE>(ak, M, tq, lds, s, lane);       // the slot keeps its token across the pop
                     __builtin_amdgcn_s_setprio(0);
                 }

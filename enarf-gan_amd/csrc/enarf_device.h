@@ -149,6 +149,21 @@ __device__ __forceinline__ void wv_next(const float v[SPL], float out[SPL], int 
     }
 }
 template <int SPL>
+__device__ __forceinline__ void wv_suffix_excl(const float v[SPL], float out[SPL], int lane) {   // out[e] = sum_{j>e} v[j] (last: 0)
+    // an inclusive scan of the reversed elements, read back one element on: the tail is summed from its far end, so a
+    // small suffix keeps its own precision (the total minus a prefix loses it: an error of ~2^-24 of the total)
+    float r[SPL];
+#pragma unroll
+    for (int s = 0; s < SPL; ++s) r[s] = __shfl(v[SPL - 1 - s], 63 - lane);      // r[p] = v[64 SPL - 1 - p]
+    wv_scan_incl<SPL>(r, lane);                                                    // r[p] = sum_{j >= 64 SPL - 1 - p} v[j]
+#pragma unroll
+    for (int s = 0; s < SPL; ++s) {
+        const int e = 64 * s + lane;
+        const float x = wv_get<SPL>(r, 64 * SPL - 2 - e);
+        out[s] = (e == 64 * SPL - 1) ? 0.0f : x;
+    }
+}
+template <int SPL>
 __device__ __forceinline__ float wv_sum(const float v[SPL]) {
     float t = 0.0f;
 #pragma unroll

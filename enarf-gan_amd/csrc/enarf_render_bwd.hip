@@ -482,7 +482,7 @@ __global__ __launch_bounds__(256, kBwdWavesPerSimd) void render_bwd_kernel(const
             const float gC2 = a.g_color ? a.g_color[((size_t)b * 3 + 2) * n + ray] : 0.0f;
             const float gM = a.g_mask ? a.g_mask[ro] : 0.0f;
             const float gD = a.g_disparity ? a.g_disparity[ro] : 0.0f;
-            float fdepth[SPL], dnext[SPL], aa[SPL], cs[SPL], gw[SPL], incl[SPL], G[SPL], Tt[SPL], ea[SPL], wgt[SPL];
+            float fdepth[SPL], dnext[SPL], aa[SPL], cs[SPL], gw[SPL], sfx[SPL], G[SPL], Tt[SPL], ea[SPL], wgt[SPL];
             float h0[SPL], h1[SPL], h2[SPL], h3[SPL], cr[SPL], cg[SPL], cb[SPL], wm[SPL];
             uint32_t sb[SPL];
 #pragma unroll
@@ -510,15 +510,13 @@ __global__ __launch_bounds__(256, kBwdWavesPerSimd) void render_bwd_kernel(const
                 wgt[s] = seg ? Tt[s] * (1.0f - ea[s]) : 0.0f;
                 G[s] = seg ? (gC0 * cr[s] + gC1 * cg[s] + gC2 * cb[s]) + gM + gD / fdepth[s] : 0.0f;
                 gw[s] = G[s] * wgt[s];
-                incl[s] = gw[s];
             }
-            wv_scan_incl<SPL>(incl, lane);
-            const float total = __shfl(incl[SPL - 1], 63);
+            wv_suffix_excl<SPL>(gw, sfx, lane);
 #pragma unroll
             for (int s = 0; s < SPL; ++s) {
                 const int e = 64 * s + lane;
                 const bool seg = e < Nf - 1;
-                const float suffix = total - incl[s];                                   // sum_{j>i} G_j w_j
+                const float suffix = sfx[s];                                            // sum_{j>i} G_j w_j
                 const float d_a = G[s] * Tt[s] * ea[s] - suffix;                        // dL/d(sigma delta)
                 const float d_sigma = seg ? d_a * (dnext[s] - fdepth[s]) * a.render_scale : 0.0f;
                 // density = MyReLU(h3) * 10 [* max part weight] * any_valid; MyReLU backward: slope 0.1 for x < 0 when the

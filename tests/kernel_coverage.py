@@ -86,7 +86,8 @@ KERNEL_TESTS = {
         "test_gpu_api::test_sampling_api_mirror_matches_reference_golden"],
     "enarf::unpack_add_kernel(float const*, float*, int, int, int)": [
         "test_gpu_parity::test_sampler_backward_fast_path_vs_direct_and_autograd", "test_gpu_backward::test_render_backward_matches_oracle_autograd",
-        "test_gpu_backward::test_query_backward_matches_oracle_autograd"],
+        "test_gpu_backward::test_query_backward_matches_oracle_autograd",
+        "test_gpu_backward_f64::test_render_bwd_feature_gradient_channel_last"],
     "enarf::warp_fwd_kernel(float const*, float const*, float*, int, int)": [
         "test_gpu_parity::test_deformation_field_producer_vs_grid_sample", "test_gpu_backward::test_model_with_deformation_field_producer"],
     "enarf::warp_bwd_kernel(float const*, float const*, float const*, float*, float*, int, int)": [
@@ -149,15 +150,23 @@ KERNEL_TESTS = {
         "test_gpu_parity::test_query_vs_oracle_and_golden", "test_gpu_parity::test_query_points_on_the_faces_of_the_canonical_cube"],
     # ---- renderer backward (csrc/enarf_render_bwd.hip)
     "void enarf::render_bwd_kernel<1>(enarf_render_bwd_args)": [
-        "test_gpu_backward::test_render_backward_matches_oracle_autograd", "test_gpu_backward::test_render_backward_matches_reference_gradients"],
+        "test_gpu_backward::test_render_backward_matches_oracle_autograd", "test_gpu_backward::test_render_backward_matches_reference_gradients",
+        "test_gpu_backward_f64::test_render_bwd_fine_counts_vs_float64", "test_gpu_backward_f64::test_render_bwd_parts_style_and_batch_vs_float64",
+        "test_gpu_backward_f64::test_render_bwd_shared_triplane_three_images_vs_float64",
+        "test_gpu_backward_f64::test_render_bwd_group_frames_vs_float64_and_each_other"],
     "void enarf::render_bwd_kernel<2>(enarf_render_bwd_args)": [
-        "test_gpu_backward::test_render_backward_fine_counts_and_density_modes", "test_gpu_backward_sizes::test_backward_c4_shape_256_nf96"],
+        "test_gpu_backward::test_render_backward_fine_counts_and_density_modes", "test_gpu_backward_sizes::test_backward_c4_shape_256_nf96",
+        "test_gpu_backward_f64::test_render_bwd_fine_counts_vs_float64"],
     "enarf::query_bwd_kernel(enarf_query_bwd_args, long long)": [
-        "test_gpu_backward::test_query_backward_matches_oracle_autograd", "test_gpu_backward::test_query_modes_forward_and_backward"],
+        "test_gpu_backward::test_query_backward_matches_oracle_autograd", "test_gpu_backward::test_query_modes_forward_and_backward",
+        "test_gpu_backward_f64::test_query_bwd_placed_points_vs_float64"],
     "enarf::weight_grad_partial_kernel(enarf::WeightGradParams)": [
-        "test_gpu_backward::test_render_backward_matches_oracle_autograd", "test_gpu_backward::test_query_backward_matches_oracle_autograd"],
+        "test_gpu_backward::test_render_backward_matches_oracle_autograd", "test_gpu_backward::test_query_backward_matches_oracle_autograd",
+        "test_gpu_backward_f64::test_weight_grad_vs_float64", "test_gpu_backward_f64::test_render_bwd_fine_counts_vs_float64"],
     "enarf::weight_grad_reduce_kernel(enarf::WeightGradParams)": [
-        "test_gpu_backward::test_render_backward_matches_oracle_autograd", "test_gpu_backward::test_query_backward_matches_oracle_autograd"],
+        "test_gpu_backward::test_render_backward_matches_oracle_autograd", "test_gpu_backward::test_query_backward_matches_oracle_autograd",
+        "test_gpu_backward_f64::test_weight_grad_vs_float64", "test_gpu_backward_f64::test_render_bwd_fine_counts_vs_float64"],
     "enarf::prepare_bwd_kernel(enarf_prepare_bwd_args)": [
-        "test_gpu_backward::test_render_backward_matches_oracle_autograd", "test_gpu_backward::test_query_backward_matches_oracle_autograd"],
+        "test_gpu_backward::test_render_backward_matches_oracle_autograd", "test_gpu_backward::test_query_backward_matches_oracle_autograd",
+        "test_gpu_backward_f64::test_prepare_bwd_vs_float64"],
 }

@@ -1,4 +1,4 @@
-"""Build recipe of libenarf_hip.so and libenarf_mesh.so (hipcc, gfx950 only), in-tree under csrc/.
+"""Build recipe of libenarf_hip.so, libenarf_mesh.so and libenarf_raster.so (hipcc, gfx950 only), in-tree under csrc/.
 
 `python -m enarf_gan_amd.build` or `build()`; `__graft_entry__.build()` calls this. The .so files are
 git-ignored but travel to the GPU box with the repo snapshot.
@@ -21,6 +21,10 @@ HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.joi
 MESH_SOURCES = ["enarf_mesh.hip"]
 MESH_LIB = os.path.join(CSRC, "libenarf_mesh.so")
 MESH_HEADERS = [os.path.join(ROOT, "include", "enarf_mesh.h")]
+# the mesh rasteriser (include/enarf_raster.h) is a third library, outside both inventories above
+RASTER_SOURCES = ["enarf_raster.hip"]
+RASTER_LIB = os.path.join(CSRC, "libenarf_raster.so")
+RASTER_HEADERS = [os.path.join(ROOT, "include", "enarf_raster.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
          "-I", os.path.join(ROOT, "include"), "-I", CSRC]
 
@@ -30,11 +34,13 @@ def _newer(a: str, b: str) -> bool:
 
 
 def build(force: bool = False, verbose: bool = False, extra_flags=()) -> str:
-    """Build both libraries incrementally; returns the path of libenarf_hip.so (MESH_LIB is next to it)."""
+    """Build the three libraries incrementally; returns the path of libenarf_hip.so (MESH_LIB and RASTER_LIB are next
+    to it)."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     deps = [os.path.join(CSRC, h) if not os.path.isabs(h) else h for h in HEADERS] + [os.path.abspath(__file__)]
     libs, jobs = [], []
-    for lib, sources, lib_deps in ((LIB, SOURCES, deps), (MESH_LIB, MESH_SOURCES, deps + MESH_HEADERS)):
+    for lib, sources, lib_deps in ((LIB, SOURCES, deps), (MESH_LIB, MESH_SOURCES, deps + MESH_HEADERS),
+                                   (RASTER_LIB, RASTER_SOURCES, deps + RASTER_HEADERS)):
         objs, n_jobs = [], len(jobs)
         for src in sources:
             s = os.path.join(CSRC, src)
@@ -53,7 +59,7 @@ def build(force: bool = False, verbose: bool = False, extra_flags=()) -> str:
         if verbose and r.stderr.strip():
             print(r.stderr, file=sys.stderr)
 
-    with ThreadPoolExecutor(max_workers=len(SOURCES) + len(MESH_SOURCES)) as ex:
+    with ThreadPoolExecutor(max_workers=len(SOURCES) + len(MESH_SOURCES) + len(RASTER_SOURCES)) as ex:
         list(ex.map(run, jobs))
     for lib, objs, rebuilt in libs:
         if rebuilt or force or not os.path.exists(lib) or any(_newer(o, lib) for o in objs):

@@ -6,6 +6,8 @@ is generated inside `enarf_query_fwd` (lattice mode, density only, one launch; o
 `chunk` is given); the volume stays on the device. `create_mesh` keeps the reference's third-party stages (`mcubes`,
 `pytorch3d`) and raises ImportError where the reference would. `extract_mesh` is the same mesh built on the device:
 `density_volume` -> `marching_cubes` (libenarf_mesh.so) -> the reference's transform; `export_obj` writes it out.
+`rasterize_mesh` is `render_mesh_`'s hard-Phong image of such a mesh, rendered on the device (libenarf_raster.so);
+`render_mesh_` itself keeps pytorch3d.
 """
 from __future__ import annotations
 
@@ -15,6 +17,7 @@ import torch
 
 from ... import ops
 from ... import _mesh_lib
+from ... import _raster_lib
 
 
 def _grid_chunk(D: int, start: int, stop: int, center: torch.Tensor, scale: float, dev: torch.device) -> torch.Tensor:
@@ -125,6 +128,20 @@ def export_obj(vertices, triangles, path: str) -> None:
             fh.write("v %r %r %r\n" % (float(x[0]), float(x[1]), float(x[2])))
         for t in f.astype(np.int64) + 1:
             fh.write("f %d %d %d\n" % (t[0], t[1], t[2]))
+
+
+def rasterize_mesh(vertices: torch.Tensor, triangles: torch.Tensor, intrinsics, img_size: int, render_size: int = 512):
+    """render_mesh_'s image (mesh_rendering.py:17-47) on the device (libenarf_raster.so), without pytorch3d.
+
+    vertices (V, 3) fp32 in camera space and triangles (T, 3) int64 on the device, as extract_mesh returns them;
+    intrinsics (3, 3) or (1, 3, 3) of an img_size x img_size image (fx, fy, cx, cy are used). Returns the namedtuple
+    (image (R, R, 3) uint8, pix_to_face (R, R) int64, zbuf (R, R) fp32, bary (R, R, 3) fp32, normals (R, R, 3) fp32) of
+    device tensors, R = render_size, in the orientation render_mesh_ returns (row 0 = the top of K's image). One fragment
+    per pixel: the covering triangle (all 2-D barycentrics > 0 at the pixel centre, no culling) with the smallest
+    view-space depth, then the smallest id; perspective-correct barycentrics; pytorch3d's default hard-Phong colours
+    (ambient 0.5, diffuse 0.3, specular 0.2, shininess 64) with a white mesh and the light at the camera; background
+    white. The full contract, and what is not drawn, is in include/enarf_raster.h. No CPU fallback."""
+    return _raster_lib.rasterize_mesh(vertices, triangles, intrinsics, img_size, render_size)
 
 
 def render_mesh_(meshes, intrinsics, img_size, render_size=512):

@@ -134,6 +134,14 @@ class TriNARFGenerator(_RendererShell):
         z_nerf, z_render, _ = self._latent_parts(z)
         return self.nerf.extract_mesh(pose_to_camera, z_nerf, z_render, bone_length, voxel_size, mesh_th, truncation_psi)
 
+    def render_extracted_mesh(self, pose_to_camera, intrinsics, z, bone_length, voxel_size=0.003, mesh_th=15,
+                              truncation_psi=0.4):
+        """render_mesh built on the device (HIP marching cubes, HIP hard-Phong rasteriser): (image (512, 512, 3) uint8
+        numpy, (vertices, triangles)); one sample, as render_mesh."""
+        z_nerf, z_render, _ = self._latent_parts(z)
+        return self.nerf.render_extracted_mesh(pose_to_camera, intrinsics, z_nerf, z_render, bone_length, voxel_size,
+                                               mesh_th, truncation_psi, self.size)
+
 
 class DSONARFGenerator(_RendererShell):
     def __init__(self, config, size, num_bone=1, parent_id=None, num_bone_param=None):

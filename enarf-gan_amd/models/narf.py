@@ -339,6 +339,17 @@ class TriPlaneNARF(nn.Module):
         center, pose_parts, model_input = self._mesh_inputs(pose_to_camera, z, z_rend, bone_length, truncation_psi)
         return extract_mesh(self, pose_parts, center, voxel_size, mesh_th, model_input)
 
+    def render_extracted_mesh(self, pose_to_camera, intrinsics, z, z_rend, bone_length, voxel_size=0.003, mesh_th=15,
+                              truncation_psi=0.4, img_size=128):
+        """render_mesh on the device: extract_mesh -> rasterize_mesh (HIP hard-Phong, 512 x 512), one host copy of the
+        finished image. Returns (image (512, 512, 3) uint8 numpy, (vertices, triangles)) as render_mesh returns
+        (image, meshes)."""
+        from ..libraries.NARF.mesh_rendering import rasterize_mesh
+        vertices, triangles = self.extract_mesh(pose_to_camera, z, z_rend, bone_length, voxel_size, mesh_th,
+                                                truncation_psi)
+        image = rasterize_mesh(vertices, triangles, intrinsics, img_size).image
+        return image.cpu().numpy(), (vertices, triangles)
+
     def _mesh_inputs(self, pose_to_camera, z, z_rend, bone_length, truncation_psi):
         if not ((z is None or z.shape[0] == 1) and (bone_length is None or bone_length.shape[0] == 1)):
             raise AssertionError("render_mesh takes one sample (base.py:67-68)")

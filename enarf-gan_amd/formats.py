@@ -10,6 +10,8 @@ pose / camera caches. Readers execute nothing from the file.
   `load_state_dict`. Read with `torch.load(weights_only=True)`.
 * `cache.pickle` (dataset/dataset.py:152-185; README.md:40-48) - {"img": [blosc-packed uint8 (3, S, S)], "camera_intrinsic"
   (N, 3, 3), "smpl_pose" (N, 24, 4, 4) [, "camera_rotation" (N, 3, 3), "camera_translation" (N, 3, 1), "frame_id" (N,)]}.
+* a pose-prior `cache.pickle` (HumanPoseDataset.create_cache, dataset/dataset.py:237-263) - the same dictionary without
+  "img", and an optional `canonical.npy` next to it (read with allow_pickle=False).
 * `sample_data.pickle` (data_preprocess/ZJU/prepare_sample_data.py:59-66) - [{"pose_3d" (24, 4, 4), "intrinsics" (3, 3),
   "bone_length" (23, 1)}, ...].
   Both are read with an unpickler that only rebuilds numpy arrays and plain containers: any other global in the stream
@@ -154,6 +156,44 @@ def read_cache(path) -> HumanCache:
         pose_c = pose_w
     return HumanCache(list(d["img"]), K, np.linalg.inv(K), pose_w, pose_c, rot,
                       np.asarray(d["frame_id"]) if "frame_id" in d else None)
+
+
+class PoseCache(NamedTuple):
+    """cache.pickle as HumanPoseDataset.create_cache leaves it (dataset/dataset.py:237-263): no images needed."""
+    intrinsics: np.ndarray                 # (N, 3, 3)
+    inv_intrinsics: np.ndarray             # (N, 3, 3) np.linalg.inv, as the reference
+    pose_to_world: np.ndarray              # (N, 24, 4, 4) "smpl_pose"
+    pose_to_camera: np.ndarray             # (N, 24, 4, 4) extrinsic @ pose_to_world, or pose_to_world
+    camera_rotation: Optional[np.ndarray]  # (N, 3, 3) or None
+    canonical_pose: Optional[np.ndarray]   # canonical.npy next to the cache, or None
+
+
+def read_pose_cache(path) -> PoseCache:
+    """A pose-prior cache.pickle (the one pose_prior_root names) and the canonical.npy in its directory, if any."""
+    import os
+    d = _load_arrays(path)
+    if not isinstance(d, dict):
+        raise ValueError(f"{path}: not a cache.pickle dictionary")
+    for key in ("camera_intrinsic", "smpl_pose"):
+        if key not in d:
+            raise ValueError(f"{path}: cache.pickle lacks '{key}'")
+    K = np.asarray(d["camera_intrinsic"])
+    pose_w = np.asarray(d["smpl_pose"])
+    n = len(K)
+    if K.shape != (n, 3, 3) or pose_w.shape != (n, 24, 4, 4):
+        raise ValueError(f"{path}: camera_intrinsic {K.shape} and smpl_pose {pose_w.shape} do not describe one pose each")
+    rot = None
+    if "camera_rotation" in d:
+        rot = np.asarray(d["camera_rotation"])
+        ext = np.broadcast_to(np.eye(4), (n, 4, 4)).copy()
+        ext[:, :3, :3] = rot
+        ext[:, :3, 3:] = np.asarray(d["camera_translation"])
+        pose_c = np.matmul(ext[:, None], pose_w)
+    else:
+        pose_c = pose_w
+    canonical = os.path.join(os.path.dirname(os.path.abspath(path)), "canonical.npy")
+    canonical = np.load(canonical, allow_pickle=False) if os.path.exists(canonical) else None
+    return PoseCache(K, np.linalg.inv(K), pose_w, pose_c, rot, canonical)
 
 
 def unpack_image(packed: bytes) -> np.ndarray:

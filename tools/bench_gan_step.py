@@ -54,6 +54,9 @@ def build(args, dev, frames):
     data = {k: sc[k].to(dev) for k in ("pose_to_camera", "bone_length", "inv_intrinsics")}
     data["real"] = torch.randn(frames, 3, S, S, device=dev, generator=g).clamp(-1, 1)
     data["bone_mask"] = (torch.rand(frames, S, S, device=dev, generator=g) > 0.97).float()
+    if args.bone_masks == "drawn":           # the pose prior's masks of these very poses (dataset.utils_3d.bone_masks)
+        from enarf_gan_amd.dataset.utils_3d import bone_masks
+        data["bone_mask"] = bone_masks(data["pose_to_camera"], sc["intrinsics"].to(dev), S, 0.5)["mask"]
     return gen, dis, tri, data
 
 
@@ -71,6 +74,9 @@ def main():
     ap.add_argument("--producer", choices=("stylegan", "planes"), default="stylegan")
     ap.add_argument("--amp", action="store_true", help="opt-in, not the reference's arithmetic: torch.autocast(bf16) around the 2-D "
                     "networks' library convolutions (the HIP renderer and the HIP ops compute in fp32 either way)")
+    ap.add_argument("--bone-masks", choices=("random", "drawn"), default="random",
+                    help="the bone-guided loss's masks: random pixels (default, the recorded numbers) or drawn on the "
+                    "device from the scene's poses as HumanPoseDataset does")
     ap.add_argument("--backend", default=None, help="torch.distributed backend (default nccl = RCCL; gloo for a rehearsal)")
     args = ap.parse_args()
     world, rank, local = int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0))
@@ -194,7 +200,7 @@ def main():
             "config": {"workload": f"{args.size}x{args.size}, batch {args.batch} = {world} rank(s) x {args.accum} micro-batch(es) x {mb} frames, "
                                    f"Nc {args.nc} + Nf {args.nf}, tri-planes from " + ("the StyleGAN2-ADA synthesis network, " if args.producer == "stylegan" else "one learnable tri-plane per frame, ") +
                                    f"R1 on {n_r1} of {args.steps} iterations", "backend": (args.backend or "nccl") if world > 1 else None},
-            "dtype": "f32 (renderer MLP products as 3-term split fp16)" + ("; library convolutions of the 2-D networks under bf16 autocast (opt-in)" if args.amp else ""), "data": "synthetic",
+            "dtype": "f32 (renderer MLP products as 3-term split fp16)" + ("; library convolutions of the 2-D networks under bf16 autocast (opt-in)" if args.amp else ""), "data": "synthetic" + ("; bone masks drawn from the poses (libenarf_pose.so)" if args.bone_masks == "drawn" else ""),
             "phases_ms_mean_rank0": {k: sum(v) / len(v) for k, v in phases.items()},
             "fake_image_abs_mean": float(out.abs().mean()),
             "params_M": {"generator (renderer MLP + background network" + (" + tri-plane synthesis network)" if args.producer == "stylegan" else ")"): sum(p.numel() for p in gen_params) / 1e6,

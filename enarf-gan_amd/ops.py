@@ -764,3 +764,52 @@ def prepare_bwd(z_rend: torch.Tensor, mlp: Dict[str, torch.Tensor], dW):
         grads[f"layers.{i}.conv.modulation.weight"] = _sum_images(outs[i][1])
         grads[f"layers.{i}.conv.modulation.bias"] = _sum_images(outs[i][2])
     return grads, dz.sum(1)
+
+
+# ------------------------------------------------------------------------------------------------- DSO supervision
+class _PhotometricLoss(torch.autograd.Function):
+    """libenarf_photo.so's loss: two launches forward, one backward; the targets (color, mask) get no gradient."""
+
+    @staticmethod
+    def forward(ctx, sparse_color, sparse_mask, grid, color, mask, loss_type, color_coef, mask_coef, check_ids):
+        from . import _photo_lib
+        loss = _photo_lib.loss_fwd(grid, sparse_color, sparse_mask, color, mask, loss_type, color_coef, mask_coef, check_ids)
+        ctx.save_for_backward(sparse_color, sparse_mask, grid, color, mask)
+        ctx.cfg = (loss_type, color_coef, mask_coef)
+        return loss[0], loss[1]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_color, g_mask):
+        from . import _photo_lib
+        sparse_color, sparse_mask, grid, color, mask = ctx.saved_tensors
+        d_color, d_mask = _photo_lib.loss_bwd(grid, sparse_color, sparse_mask, color, mask, *ctx.cfg,
+                                              None if g_color is None else g_color.contiguous(),
+                                              None if g_mask is None else g_mask.contiguous())
+        return d_color, d_mask, None, None, None, None, None, None, None
+
+
+def photometric_loss(grid: Optional[torch.Tensor], sparse_color: torch.Tensor, sparse_mask: torch.Tensor,
+                     color: torch.Tensor, mask: Optional[torch.Tensor] = None, loss_type: str = "mse",
+                     color_coef: float = 1.0, mask_coef: float = 1.0, check_ids: bool = False):
+    """(loss_color, loss_mask) of the reference's PhotometricLoss (libraries/NeRF/loss.py:17-48) as 0-dim fp32 device
+    tensors, differentiable in sparse_color (B, 3, N) and sparse_mask (B, N); loss_mask is the integer 0 without a
+    mask, as in the reference. color (B, 3, S, S) and mask (B, S, S) are the real frame, grid (B, N) int64 flat pixel
+    ids in [0, S * S) (unchecked unless `check_ids`, which synchronises); grid None takes color (B, 3, N) and mask
+    (B, N) as already gathered. loss_type "mse" or "mae" (the truncated MAE, threshold 0.01)."""
+    if color.requires_grad or (mask is not None and mask.requires_grad):
+        raise NotImplementedError("photometric_loss: the real image and mask are targets and get no gradient; detach them")
+    loss_color, loss_mask = _PhotometricLoss.apply(sparse_color, sparse_mask, grid, color, mask, loss_type,
+                                                   float(color_coef), float(mask_coef), bool(check_ids))
+    return loss_color, (0 if mask is None else loss_mask)
+
+
+def image_metrics(img: torch.Tensor, gen: torch.Tensor, mask: Optional[torch.Tensor] = None,
+                  gen_mask: Optional[torch.Tensor] = None, bbox=None) -> torch.Tensor:
+    """(B, 4) fp32 device tensor [ssim, mse_color, psnr, mse_mask] per image over the rectangle bbox = (x0, y0, x1, y1)
+    (exclusive upper bounds; one for all images or one per image; None = the whole frame), read in place, with no host
+    synchronisation. SSIM is scikit-image's structural_similarity(x * 0.5 + 0.5, data_range=1, 7 x 7 uniform window)
+    averaged over the channels; psnr = 20 log10(2) - 10 log10(mse_color); mse_mask is NaN without masks. `gen` and
+    `gen_mask` may already be cropped to the rectangle. A rectangle side shorter than 7 raises ValueError."""
+    from . import _photo_lib
+    return _photo_lib.metrics(img, gen, mask, gen_mask, bbox)

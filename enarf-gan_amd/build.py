@@ -1,5 +1,5 @@
-"""Build recipe of libenarf_hip.so, libenarf_mesh.so, libenarf_raster.so, libenarf_pose.so and libenarf_photo.so (hipcc,
-gfx950 only), in-tree under csrc/.
+"""Build recipe of libenarf_hip.so, libenarf_mesh.so, libenarf_raster.so, libenarf_pose.so, libenarf_photo.so and
+libenarf_guide.so (hipcc, gfx950 only), in-tree under csrc/.
 
 `python -m enarf_gan_amd.build` or `build()`; `__graft_entry__.build()` calls this. The .so files are
 git-ignored but travel to the GPU box with the repo snapshot.
@@ -34,6 +34,10 @@ POSE_HEADERS = [os.path.join(ROOT, "include", "enarf_pose.h")]
 PHOTO_SOURCES = ["enarf_photo.hip"]
 PHOTO_LIB = os.path.join(CSRC, "libenarf_photo.so")
 PHOTO_HEADERS = [os.path.join(ROOT, "include", "enarf_photo.h")]
+# the mask-guidance loss of the GAN's generator (include/enarf_guide.h) is a sixth library
+GUIDE_SOURCES = ["enarf_guide.hip"]
+GUIDE_LIB = os.path.join(CSRC, "libenarf_guide.so")
+GUIDE_HEADERS = [os.path.join(ROOT, "include", "enarf_guide.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
          "-I", os.path.join(ROOT, "include"), "-I", CSRC]
 
@@ -43,15 +47,16 @@ def _newer(a: str, b: str) -> bool:
 
 
 def build(force: bool = False, verbose: bool = False, extra_flags=()) -> str:
-    """Build the five libraries incrementally; returns the path of libenarf_hip.so (MESH_LIB, RASTER_LIB, POSE_LIB and
-    PHOTO_LIB are next to it)."""
+    """Build the six libraries incrementally; returns the path of libenarf_hip.so (MESH_LIB, RASTER_LIB, POSE_LIB,
+    PHOTO_LIB and GUIDE_LIB are next to it)."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     deps = [os.path.join(CSRC, h) if not os.path.isabs(h) else h for h in HEADERS] + [os.path.abspath(__file__)]
     libs, jobs = [], []
     for lib, sources, lib_deps in ((LIB, SOURCES, deps), (MESH_LIB, MESH_SOURCES, deps + MESH_HEADERS),
                                    (RASTER_LIB, RASTER_SOURCES, deps + RASTER_HEADERS),
                                    (POSE_LIB, POSE_SOURCES, deps + POSE_HEADERS),
-                                   (PHOTO_LIB, PHOTO_SOURCES, deps + PHOTO_HEADERS)):
+                                   (PHOTO_LIB, PHOTO_SOURCES, deps + PHOTO_HEADERS),
+                                   (GUIDE_LIB, GUIDE_SOURCES, deps + GUIDE_HEADERS)):
         objs, n_jobs = [], len(jobs)
         for src in sources:
             s = os.path.join(CSRC, src)
@@ -70,7 +75,8 @@ def build(force: bool = False, verbose: bool = False, extra_flags=()) -> str:
         if verbose and r.stderr.strip():
             print(r.stderr, file=sys.stderr)
 
-    n_sources = len(SOURCES) + len(MESH_SOURCES) + len(RASTER_SOURCES) + len(POSE_SOURCES) + len(PHOTO_SOURCES)
+    n_sources = (len(SOURCES) + len(MESH_SOURCES) + len(RASTER_SOURCES) + len(POSE_SOURCES) + len(PHOTO_SOURCES) +
+                 len(GUIDE_SOURCES))
     with ThreadPoolExecutor(max_workers=n_sources) as ex:
         list(ex.map(run, jobs))
     for lib, objs, rebuilt in libs:

@@ -1,6 +1,8 @@
 """Mask regularisers of the GAN's generator loss (models/loss.py:5-30): the lowest `background_ratio` of the rendered
 foreground-mask values are pushed to zero, and the mask is pulled to one where the projected skeleton is
-(`bone_mask` > 0.5, max-pooled down to the mask's resolution)."""
+(`bone_mask` > 0.5, max-pooled down to the mask's resolution). `push_to_background`, `nerf_bone_loss` and
+`nerf_patch_loss` are the plain-torch statement; `mask_guidance_loss` is the same loss as one HIP op
+(libenarf_guide.so) with `nerf_patch_loss`'s signature."""
 import torch
 import torch.nn.functional as F
 
@@ -24,3 +26,10 @@ def nerf_bone_loss(fake_mask: torch.Tensor, bone_mask: torch.Tensor) -> torch.Te
 
 def nerf_patch_loss(fake_mask, bone_mask, background_ratio=0.3, coef=10):
     return (push_to_background(fake_mask, background_ratio) + nerf_bone_loss(fake_mask, bone_mask)) * coef
+
+
+def mask_guidance_loss(fake_mask, bone_mask, background_ratio=0.3, coef=10):
+    """`nerf_patch_loss` on the device (ops.mask_guidance_loss): fp32 device tensors, 3-D masks or equal shapes; among
+    equal values at the selection threshold the lowest flat indices are taken, where `torch.topk` leaves it open."""
+    from .. import ops
+    return ops.mask_guidance_loss(fake_mask, bone_mask, background_ratio, coef)

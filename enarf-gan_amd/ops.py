@@ -813,3 +813,42 @@ def image_metrics(img: torch.Tensor, gen: torch.Tensor, mask: Optional[torch.Ten
     `gen_mask` may already be cropped to the rectangle. A rectangle side shorter than 7 raises ValueError."""
     from . import _photo_lib
     return _photo_lib.metrics(img, gen, mask, gen_mask, bbox)
+
+
+# ------------------------------------------------------------------------------------------------- GAN supervision
+class _MaskGuidanceLoss(torch.autograd.Function):
+    """libenarf_guide.so's loss: a memset and six launches forward (two without the push term), one backward; the bone
+    mask gets no gradient. The selection is carried to the backward as the forward's state, not as an index tensor."""
+
+    @staticmethod
+    def forward(ctx, fake_mask, bone_mask, background_ratio, coef):
+        from . import _guide_lib
+        out, state = _guide_lib.loss_fwd(fake_mask, bone_mask, background_ratio, coef)
+        ctx.save_for_backward(fake_mask, bone_mask, state)
+        ctx.cfg = (background_ratio, coef)
+        loss, push, bone = out[0], out[1], out[2]
+        ctx.mark_non_differentiable(push, bone)
+        return loss, push, bone
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, up, _push, _bone):
+        from . import _guide_lib
+        fake_mask, bone_mask, state = ctx.saved_tensors
+        return _guide_lib.loss_bwd(fake_mask, bone_mask, *ctx.cfg, state, up), None, None, None
+
+
+def mask_guidance_loss(fake_mask: torch.Tensor, bone_mask: torch.Tensor, background_ratio: float = 0.3,
+                       coef: float = 10, return_terms: bool = False):
+    """`nerf_patch_loss` of the reference's models/loss.py:5-30 as a 0-dim fp32 device tensor, differentiable in
+    fake_mask: (push + bone) * coef with push = the mean square of the k = int(N * background_ratio) smallest mask
+    values (left out when background_ratio <= 0) and bone = the mean of (1 - m)^2 over the pixels under the bone mask
+    (max-pooled down to the mask's resolution, > 0.5). fake_mask is (..., s, s); bone_mask has the same shape or, for
+    3-D masks, (B, S, S) with S // s >= 1. Of several values equal to the k-th smallest the ones with the lowest flat
+    index are selected (include/enarf_guide.h), so the gradient is a function of the input. An empty bone mask gives a
+    NaN loss and NaN gradients, as in the reference. `return_terms` adds the two unscaled terms (push, bone), detached.
+    Nothing here synchronises."""
+    if bone_mask.requires_grad:
+        raise NotImplementedError("mask_guidance_loss: the bone mask is a target and gets no gradient; detach it")
+    loss, push, bone = _MaskGuidanceLoss.apply(fake_mask, bone_mask, float(background_ratio), float(coef))
+    return (loss, push, bone) if return_terms else loss

@@ -25,7 +25,7 @@ from enarf_gan_amd import sharding, synth  # noqa: E402
 from enarf_gan_amd.libraries.custom_stylegan2.net import Discriminator  # noqa: E402
 from enarf_gan_amd.libraries.gan.loss import adv_loss_dis, adv_loss_gen, d_r1_loss  # noqa: E402
 from enarf_gan_amd.models.generator import TriNARFGenerator  # noqa: E402
-from enarf_gan_amd.models.loss import nerf_patch_loss  # noqa: E402
+from enarf_gan_amd.models.loss import mask_guidance_loss, nerf_patch_loss  # noqa: E402
 
 
 class Cfg(dict):
@@ -77,6 +77,9 @@ def main():
     ap.add_argument("--bone-masks", choices=("random", "drawn"), default="random",
                     help="the bone-guided loss's masks: random pixels (default, the recorded numbers) or drawn on the "
                     "device from the scene's poses as HumanPoseDataset does")
+    ap.add_argument("--bone-loss", choices=("torch", "hip"), default="torch",
+                    help="the mask-guidance loss: models.loss.nerf_patch_loss (default, the recorded numbers) or the fused "
+                    "HIP op models.loss.mask_guidance_loss (libenarf_guide.so)")
     ap.add_argument("--backend", default=None, help="torch.distributed backend (default nccl = RCCL; gloo for a rehearsal)")
     args = ap.parse_args()
     world, rank, local = int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0))
@@ -102,6 +105,7 @@ def main():
     dis_opt = torch.optim.Adam(dis_params, lr=2e-3 * lr_scale, betas=(0.0, 0.99))
     g_red = sharding.GradientReducer(gen_params, world) if dist is not None else None
     d_red = sharding.GradientReducer(dis_params, world) if dist is not None else None
+    bone_loss = mask_guidance_loss if args.bone_loss == "hip" else nerf_patch_loss
     ev = {}
     t_w = time.perf_counter()
     import contextlib
@@ -133,7 +137,7 @@ def main():
                 fake, mask, _, _ = gen(data["pose_to_camera"][sl], None, data["bone_length"][sl], z, data["inv_intrinsics"][sl])
                 fake, mask = fake.float(), mask.float()
                 logits = dis(fake, dist is not None, world).float()
-            loss = adv_loss_gen(logits, "ce") + nerf_patch_loss(mask, data["bone_mask"][sl], gen.background_ratio)
+            loss = adv_loss_gen(logits, "ce") + bone_loss(mask, data["bone_mask"][sl], gen.background_ratio)
             grads = torch.autograd.grad(loss, gen_params + [tri], allow_unused=True)       # tri: unused with the real producer
             if grads[-1] is not None:
                 tri.grad = grads[-1] if (k == 0 or tri.grad is None) else tri.grad + grads[-1]
@@ -200,7 +204,7 @@ def main():
             "config": {"workload": f"{args.size}x{args.size}, batch {args.batch} = {world} rank(s) x {args.accum} micro-batch(es) x {mb} frames, "
                                    f"Nc {args.nc} + Nf {args.nf}, tri-planes from " + ("the StyleGAN2-ADA synthesis network, " if args.producer == "stylegan" else "one learnable tri-plane per frame, ") +
                                    f"R1 on {n_r1} of {args.steps} iterations", "backend": (args.backend or "nccl") if world > 1 else None},
-            "dtype": "f32 (renderer MLP products as 3-term split fp16)" + ("; library convolutions of the 2-D networks under bf16 autocast (opt-in)" if args.amp else ""), "data": "synthetic" + ("; bone masks drawn from the poses (libenarf_pose.so)" if args.bone_masks == "drawn" else ""),
+            "dtype": "f32 (renderer MLP products as 3-term split fp16)" + ("; library convolutions of the 2-D networks under bf16 autocast (opt-in)" if args.amp else ""), "data": "synthetic" + ("; bone masks drawn from the poses (libenarf_pose.so)" if args.bone_masks == "drawn" else "") + ("; mask-guidance loss as the HIP op (libenarf_guide.so)" if args.bone_loss == "hip" else ""),
             "phases_ms_mean_rank0": {k: sum(v) / len(v) for k, v in phases.items()},
             "fake_image_abs_mean": float(out.abs().mean()),
             "params_M": {"generator (renderer MLP + background network" + (" + tri-plane synthesis network)" if args.producer == "stylegan" else ")"): sum(p.numel() for p in gen_params) / 1e6,

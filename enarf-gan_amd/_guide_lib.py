@@ -1,20 +1,16 @@
 """ctypes binding of libenarf_guide.so (the C ABI declared in include/enarf_guide.h): the mask-guidance loss of the
 GAN's generator (`nerf_patch_loss` of the reference's models/loss.py), forward and backward, on the device.
 
-Like `_lib`, `_mesh_lib`, `_raster_lib`, `_pose_lib` and `_photo_lib` there is no CPU fallback: a missing library, a
-CPU tensor or a failed call raises EnarfHipError. Shapes and the ratio are checked before anything touches the device
-(ValueError), so those checks run without one.
+Loading, return codes and the device-argument checks are `_loader`'s. Shapes and the ratio are checked before anything
+touches the device (ValueError), so those checks run without one.
 """
 from __future__ import annotations
 
 import ctypes as C
-import os
-from typing import Optional, Tuple
+from typing import Tuple
 
-from ._lib import EnarfHipError
+from ._loader import Library, device_of, stream_of
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "csrc", "libenarf_guide.so")
 ABI_VERSION = 1
 
 MAX_BLOCKS = 512                                     # ENARF_GUIDE_MAX_BLOCKS
@@ -32,35 +28,8 @@ SIGNATURES = {
     "enarf_guide_loss_bwd": (C.c_int, [_p, _p, _i64, C.c_int, C.c_int, _i64, C.c_int, C.c_double, _p, _p, _p, _p]),
 }
 
-_lib: Optional[C.CDLL] = None
-
-
-def load() -> C.CDLL:
-    """Load libenarf_guide.so (once). Raises if it has not been built: there is no fallback path."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    import torch  # noqa: F401  (torch's HIP runtime first, as in _lib.load)
-    if not os.path.exists(LIB_PATH):
-        raise EnarfHipError(f"{LIB_PATH} is missing: build it with `python -m enarf_gan_amd.build` (hipcc, gfx950). "
-                            "The mask-guidance loss has no CPU fallback.")
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    if lib.enarf_guide_abi_version() != ABI_VERSION:
-        raise EnarfHipError(f"libenarf_guide.so ABI {lib.enarf_guide_abi_version()} != {ABI_VERSION}")
-    _lib = lib
-    return lib
-
-
-def check(rc: int, what: str) -> None:
-    if rc != 0:
-        msg = load().enarf_guide_last_error().decode(errors="replace")
-        if rc == -2:
-            raise NotImplementedError(f"{what}: {msg}")
-        raise EnarfHipError(f"{what} failed (code {rc}): {msg}")
+_library = Library("guide", ABI_VERSION, SIGNATURES, "The mask-guidance loss has no CPU fallback.")
+load, check = _library.load, _library.check
 
 
 def geometry(n: int) -> Tuple[int, int]:
@@ -107,33 +76,19 @@ def check_shapes(fake_mask, bone_mask, background_ratio: float) -> Tuple[int, in
     return n // (s * s), s, S, k, with_push
 
 
-def _device_f32(who: str, **tensors):
-    import torch
-    dev = None
-    for name, t in tensors.items():
-        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-            raise EnarfHipError(f"{who} takes device tensors (there is no CPU fallback); {name} is not one")
-        if t.dtype != torch.float32:
-            raise EnarfHipError(f"{who} takes fp32 {name}, got {t.dtype}")
-        if dev is not None and t.device != dev:
-            raise EnarfHipError(f"{who}: {name} is on {t.device}, other arguments on {dev}")
-        dev = t.device
-    return dev
-
-
 def loss_fwd(fake_mask, bone_mask, background_ratio: float, coef: float):
     """((3,) fp32 device tensor [loss, push, bone], state for `loss_bwd`) on fake_mask's device and its current stream;
     no host synchronisation."""
     import torch
     B, s, S, k, with_push = check_shapes(fake_mask, bone_mask, background_ratio)
-    dev = _device_f32("mask_guidance_loss", fake_mask=fake_mask, bone_mask=bone_mask)
+    dev = device_of("mask_guidance_loss", (torch.float32,), fake_mask=fake_mask, bone_mask=bone_mask)
     lib = load()
     with torch.cuda.device(dev):
         fake, bone = fake_mask.contiguous(), bone_mask.contiguous()
         work = torch.empty(WORK_BYTES // 8, dtype=torch.float64, device=dev)
         state = torch.empty(STATE_INTS, dtype=torch.int32, device=dev)
         out = torch.empty(3, dtype=torch.float32, device=dev)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = stream_of(dev)
         check(lib.enarf_guide_loss_fwd(fake.data_ptr(), bone.data_ptr(), B, s, S, k, int(with_push), float(coef),
                                        work.data_ptr(), state.data_ptr(), out.data_ptr(), stream), "enarf_guide_loss_fwd")
     return out, state
@@ -144,14 +99,14 @@ def loss_bwd(fake_mask, bone_mask, background_ratio: float, coef: float, state, 
     the device) and the forward's `state`."""
     import torch
     B, s, S, k, with_push = check_shapes(fake_mask, bone_mask, background_ratio)
-    dev = _device_f32("mask_guidance_loss backward", fake_mask=fake_mask, bone_mask=bone_mask, up=up)
+    dev = device_of("mask_guidance_loss backward", (torch.float32,), fake_mask=fake_mask, bone_mask=bone_mask, up=up)
     if up.numel() != 1:
         raise ValueError(f"the upstream gradient must be a scalar, got {tuple(up.shape)}")
     lib = load()
     with torch.cuda.device(dev):
         fake, bone, up = fake_mask.contiguous(), bone_mask.contiguous(), up.contiguous()
         d_fake = torch.empty_like(fake)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = stream_of(dev)
         check(lib.enarf_guide_loss_bwd(fake.data_ptr(), bone.data_ptr(), B, s, S, k, int(with_push), float(coef),
                                        state.data_ptr(), up.data_ptr(), d_fake.data_ptr(), stream), "enarf_guide_loss_bwd")
     return d_fake.view(fake_mask.shape)

@@ -1,4 +1,4 @@
-"""ctypes binding of libenarf_hip.so (the C ABI declared in include/enarf_hip.h).
+"""ctypes binding of libenarf_hip.so (the C ABI declared in include/enarf_hip.h), loaded and checked by `_loader`.
 
 There is no CPU fallback: if the library is missing or a call fails, an exception is raised.
 """
@@ -6,26 +6,8 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-# The product loads the in-tree library and nothing else: no environment variable changes what runs.
-# Measurement tools that A/B a variant build of the same ABI call `use_variant(path)` explicitly, before the first load().
-LIB_PATH = os.path.join(_HERE, "csrc", "libenarf_hip.so")
-_variant = False
-
-
-def use_variant(path: str) -> None:
-    """Measurement only (bench.py --allow-variant, tools/): load another build of the same ABI instead of the in-tree one."""
-    global LIB_PATH, _variant
-    if _lib is not None:
-        raise EnarfHipError("use_variant() must be called before the library is loaded")
-    LIB_PATH, _variant = os.path.abspath(path), True
-
-
-def library_info() -> dict:
-    """What is (or will be) loaded: path and whether it is a variant build - bench.py prints this."""
-    return {"path": LIB_PATH, "variant": _variant}
+from ._loader import EnarfHipError, Library  # noqa: F401  (EnarfHipError is imported from here by the rest of the package)
 
 ABI_VERSION = 4
 STATUS_MARCH_WATCHDOG = 1                      # ENARF_STATUS_* (include/enarf_hip.h)
@@ -180,35 +162,26 @@ SIGNATURES = {
     "enarf_upfirdn2d_plan": (C.c_int, [C.c_longlong] + [C.c_int] * 11 + [C.POINTER(C.c_int)]),
 }
 
-_lib: Optional[C.CDLL] = None
+_library = Library("hip", ABI_VERSION, SIGNATURES, "enarf_gan_amd has no CPU or eager fallback.")
+load = _library.load
+# The product loads the in-tree library and nothing else: no environment variable changes what runs.
+# Measurement tools that A/B a variant build of the same ABI call `use_variant(path)` explicitly, before the first load().
+LIB_PATH = _library.path
+_variant = False
 
 
-class EnarfHipError(RuntimeError):
-    pass
+def use_variant(path: str) -> None:
+    """Measurement only (bench.py --allow-variant, tools/): load another build of the same ABI instead of the in-tree one."""
+    global LIB_PATH, _variant
+    if _library.lib is not None:
+        raise EnarfHipError("use_variant() must be called before the library is loaded")
+    LIB_PATH = _library.path = os.path.abspath(path)
+    _variant = True
 
 
-def load() -> C.CDLL:
-    """Load libenarf_hip.so (once). Raises if it has not been built: there is no fallback path."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    # torch bundles its own HIP runtime (torch/lib/libamdhip64.so). It must be in the process BEFORE this
-    # library is dlopen'ed so that both resolve to ONE runtime; loaded the other way round, this library binds
-    # /opt/rocm's copy and its launches fail with "no ROCm-capable device is detected" next to torch's.
-    import torch  # noqa: F401
-    if not os.path.exists(LIB_PATH):
-        raise EnarfHipError(
-            f"{LIB_PATH} is missing: build it with `python -m enarf_gan_amd.build` (hipcc, gfx950). "
-            "enarf_gan_amd has no CPU or eager fallback.")
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)      # AttributeError if the .so does not export a declared symbol
-        fn.restype = res
-        fn.argtypes = args
-    if lib.enarf_abi_version() != ABI_VERSION:
-        raise EnarfHipError(f"libenarf_hip.so ABI {lib.enarf_abi_version()} != {ABI_VERSION}")
-    _lib = lib
-    return lib
+def library_info() -> dict:
+    """What is (or will be) loaded: path and whether it is a variant build - bench.py prints this."""
+    return {"path": LIB_PATH, "variant": _variant}
 
 
 def device_status(clear: bool = True) -> int:
@@ -235,8 +208,5 @@ def check(rc: int, what: str) -> None:
     """Every call through the C ABI ends here: its own return code first, then the device's sticky status word - a kernel
     that gave up (the task march's watchdog) is reported by the next call on that device, whatever the caller asked for."""
     if rc != 0:
-        msg = load().enarf_last_error().decode(errors="replace")
-        if rc == -2:
-            raise NotImplementedError(f"{what}: {msg}")
-        raise EnarfHipError(f"{what} failed (code {rc}): {msg}")
+        _library.check(rc, what)
     raise_on_device_status(what)

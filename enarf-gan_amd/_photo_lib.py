@@ -1,20 +1,16 @@
 """ctypes binding of libenarf_photo.so (the C ABI declared in include/enarf_photo.h): the photometric loss of the
 single-scene path (forward and backward) and the per-image validation metrics (SSIM, MSE, PSNR) on the device.
 
-Like `_lib`, `_mesh_lib`, `_raster_lib` and `_pose_lib` there is no CPU fallback: a missing library, a CPU tensor or
-a failed call raises EnarfHipError. Shapes, loss types and rectangles are checked before anything touches the device
-(ValueError), so those checks run without one.
+Loading, return codes and the device-argument checks are `_loader`'s. Shapes, loss types and rectangles are checked
+before anything touches the device (ValueError), so those checks run without one.
 """
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import Optional, Sequence, Tuple
 
-from ._lib import EnarfHipError
+from ._loader import EnarfHipError, Library, device_of, stream_of
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "csrc", "libenarf_photo.so")
 ABI_VERSION = 1
 
 LOSS_TYPES = {"mse": 0, "mae": 1}
@@ -36,56 +32,13 @@ SIGNATURES = {
                                       C.POINTER(C.c_int), _p, _i64, _p, _p]),
 }
 
-_lib: Optional[C.CDLL] = None
-
-
-def load() -> C.CDLL:
-    """Load libenarf_photo.so (once). Raises if it has not been built: there is no fallback path."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    import torch  # noqa: F401  (torch's HIP runtime first, as in _lib.load)
-    if not os.path.exists(LIB_PATH):
-        raise EnarfHipError(f"{LIB_PATH} is missing: build it with `python -m enarf_gan_amd.build` (hipcc, gfx950). "
-                            "The photometric loss and the image metrics have no CPU fallback.")
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    if lib.enarf_photo_abi_version() != ABI_VERSION:
-        raise EnarfHipError(f"libenarf_photo.so ABI {lib.enarf_photo_abi_version()} != {ABI_VERSION}")
-    _lib = lib
-    return lib
-
-
-def check(rc: int, what: str) -> None:
-    if rc != 0:
-        msg = load().enarf_photo_last_error().decode(errors="replace")
-        if rc == -2:
-            raise NotImplementedError(f"{what}: {msg}")
-        raise EnarfHipError(f"{what} failed (code {rc}): {msg}")
+_library = Library("photo", ABI_VERSION, SIGNATURES, "The photometric loss and the image metrics have no CPU fallback.")
+load, check = _library.load, _library.check
 
 
 def metric_partials(h: int, w: int) -> int:
     """ENARF_PHOTO_METRIC_PARTIALS(h, w): doubles of scratch one image's rectangle needs"""
     return 3 * ((h + TILE - 1) // TILE) * ((w + TILE - 1) // TILE)
-
-
-def _device_f32(who: str, **tensors):
-    import torch
-    dev = None
-    for name, t in tensors.items():
-        if t is None:
-            continue
-        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-            raise EnarfHipError(f"{who} takes device tensors (there is no CPU fallback); {name} is not one")
-        if t.dtype != torch.float32:
-            raise EnarfHipError(f"{who} takes fp32 {name}, got {t.dtype}")
-        if dev is not None and t.device != dev:
-            raise EnarfHipError(f"{who}: {name} is on {t.device}, other arguments on {dev}")
-        dev = t.device
-    return dev
 
 
 def check_loss_shapes(grid, sparse_color, sparse_mask, color, mask, loss_type: str) -> Tuple[int, int, int]:
@@ -117,7 +70,7 @@ def check_loss_shapes(grid, sparse_color, sparse_mask, color, mask, loss_type: s
 def _loss_args(grid, sparse_color, sparse_mask, color, mask, loss_type, who, check_ids):
     import torch
     B, npix, N = check_loss_shapes(grid, sparse_color, sparse_mask, color, mask, loss_type)
-    dev = _device_f32(who, sparse_color=sparse_color, sparse_mask=sparse_mask, color=color, mask=mask)
+    dev = device_of(who, (torch.float32,), sparse_color=sparse_color, sparse_mask=sparse_mask, color=color, mask=mask)
     if grid is not None:
         if not isinstance(grid, torch.Tensor) or grid.device != dev or grid.dtype != torch.int64:
             raise EnarfHipError(f"{who} takes an int64 grid on {dev}")
@@ -140,7 +93,7 @@ def loss_fwd(grid, sparse_color, sparse_mask, color, mask, loss_type: str, color
     with torch.cuda.device(dev):
         partials = torch.empty(LOSS_PARTIALS, dtype=torch.float64, device=dev)
         loss = torch.empty(2, dtype=torch.float32, device=dev)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = stream_of(dev)
         check(lib.enarf_photo_loss_fwd(color.data_ptr(), None if mask is None else mask.data_ptr(),
                                        None if grid is None else grid.data_ptr(), sc.data_ptr(), sm.data_ptr(), B, npix,
                                        N, LOSS_TYPES[loss_type], float(color_coef), float(mask_coef),
@@ -155,12 +108,12 @@ def loss_bwd(grid, sparse_color, sparse_mask, color, mask, loss_type: str, color
     import torch
     B, npix, N, dev, grid, sc, sm, color, mask = _loss_args(grid, sparse_color, sparse_mask, color, mask, loss_type,
                                                             "photometric_loss backward", False)
-    _device_f32("photometric_loss backward", g_color=g_color, g_mask=g_mask, sparse_color=sc)
+    device_of("photometric_loss backward", (torch.float32,), g_color=g_color, g_mask=g_mask, sparse_color=sc)
     lib = load()
     with torch.cuda.device(dev):
         d_color = torch.empty_like(sc)
         d_mask = None if mask is None else torch.empty_like(sm)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = stream_of(dev)
         check(lib.enarf_photo_loss_bwd(color.data_ptr(), None if mask is None else mask.data_ptr(),
                                        None if grid is None else grid.data_ptr(), sc.data_ptr(), sm.data_ptr(), B, npix,
                                        N, LOSS_TYPES[loss_type], float(color_coef), float(mask_coef),
@@ -208,7 +161,7 @@ def metrics(img, gen, mask=None, gen_mask=None, bbox: Optional[Sequence] = None)
     or already cropped to the rectangle (what render_entire_img(bbox=...) returns)."""
     import torch
     B, H, W, gh, gw, cropped, boxes = check_metric_shapes(img, gen, mask, gen_mask, bbox)
-    dev = _device_f32("image_metrics", img=img, gen=gen, mask=mask, gen_mask=gen_mask)
+    dev = device_of("image_metrics", (torch.float32,), img=img, gen=gen, mask=mask, gen_mask=gen_mask)
     lib = load()
     sizes = [(y1 - y0, x1 - x0) for x0, y0, x1, y1 in boxes] if boxes is not None else [(H, W)]
     n_partials = B * max(metric_partials(h, w) for h, w in sizes)
@@ -218,7 +171,7 @@ def metrics(img, gen, mask=None, gen_mask=None, bbox: Optional[Sequence] = None)
         mask, gen_mask = (None, None) if mask is None else (mask.contiguous(), gen_mask.contiguous())
         partials = torch.empty(max(n_partials, 1), dtype=torch.float64, device=dev)
         out = torch.empty(B, 4, dtype=torch.float32, device=dev)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = stream_of(dev)
         check(lib.enarf_photo_metrics(img.data_ptr(), gen.data_ptr(), None if mask is None else mask.data_ptr(),
                                       None if gen_mask is None else gen_mask.data_ptr(), B, H, W, gh, gw, int(cropped),
                                       box_arr, partials.data_ptr(), n_partials, out.data_ptr(), stream),

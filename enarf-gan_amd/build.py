@@ -1,8 +1,13 @@
-"""Build recipe of libenarf_hip.so, libenarf_mesh.so, libenarf_raster.so, libenarf_pose.so, libenarf_photo.so and
-libenarf_guide.so (hipcc, gfx950 only), in-tree under csrc/.
+"""Build recipe of the HIP libraries (hipcc, gfx950 only), in-tree under csrc/: LIBRARIES below is the one place a
+library is declared, one libenarf_<stem>.so per row.
 
 `python -m enarf_gan_amd.build` or `build()`; `__graft_entry__.build()` calls this. The .so files are
-git-ignored but travel to the GPU box with the repo snapshot.
+git-ignored but travel to the GPU box with the repo snapshot. `python -m enarf_gan_amd.build --variant NAME [-DFLAG=V ...]`
+is what tools/build_variant.sh runs: a second build of libenarf_hip.so under variants/.
+
+Adding a library: a row in LIBRARIES, its public header under include/, a binding module `_<stem>_lib.py` (constants,
+SIGNATURES, a `_loader.Library`, the ops) and a kernel -> GPU tests map in tests/kernel_coverage.py. The ABI, inventory,
+disjointness and header-tracking checks of tests/test_libraries_cpu.py run over every row.
 """
 from __future__ import annotations
 
@@ -14,55 +19,59 @@ from concurrent.futures import ThreadPoolExecutor
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
-LIB = os.path.join(CSRC, "libenarf_hip.so")
-SOURCES = ["enarf_render.hip", "enarf_render_bwd.hip", "enarf_sampler.hip", "enarf_raysample.hip", "enarf_gan_ops.hip"]
-# every header next to the sources is a dependency of every object (a list by name went stale when enarf_tasks.h was added)
-HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(ROOT, "include", "enarf_hip.h")]
-# marching cubes (include/enarf_mesh.h) is a library of its own: its kernels are not part of libenarf_hip.so's inventory
-MESH_SOURCES = ["enarf_mesh.hip"]
-MESH_LIB = os.path.join(CSRC, "libenarf_mesh.so")
-MESH_HEADERS = [os.path.join(ROOT, "include", "enarf_mesh.h")]
-# the mesh rasteriser (include/enarf_raster.h) is a third library, outside both inventories above
-RASTER_SOURCES = ["enarf_raster.hip"]
-RASTER_LIB = os.path.join(CSRC, "libenarf_raster.so")
-RASTER_HEADERS = [os.path.join(ROOT, "include", "enarf_raster.h")]
-# the pose prior's bone masks (include/enarf_pose.h) are a fourth library, outside all three inventories above
-POSE_SOURCES = ["enarf_pose.hip"]
-POSE_LIB = os.path.join(CSRC, "libenarf_pose.so")
-POSE_HEADERS = [os.path.join(ROOT, "include", "enarf_pose.h")]
-# the photometric loss and image metrics of the single-scene path (include/enarf_photo.h) are a fifth library
-PHOTO_SOURCES = ["enarf_photo.hip"]
-PHOTO_LIB = os.path.join(CSRC, "libenarf_photo.so")
-PHOTO_HEADERS = [os.path.join(ROOT, "include", "enarf_photo.h")]
-# the mask-guidance loss of the GAN's generator (include/enarf_guide.h) is a sixth library
-GUIDE_SOURCES = ["enarf_guide.hip"]
-GUIDE_LIB = os.path.join(CSRC, "libenarf_guide.so")
-GUIDE_HEADERS = [os.path.join(ROOT, "include", "enarf_guide.h")]
+# stem -> (sources under csrc/, public header under include/). Each library's kernel inventory is closed and checked on
+# its own: no kernel of one row is part of another's.
+LIBRARIES = {
+    "hip": (["enarf_render.hip", "enarf_render_bwd.hip", "enarf_sampler.hip", "enarf_raysample.hip", "enarf_gan_ops.hip"],
+            "enarf_hip.h"),
+    "mesh": (["enarf_mesh.hip"], "enarf_mesh.h"),          # marching cubes
+    "raster": (["enarf_raster.hip"], "enarf_raster.h"),    # the mesh rasteriser
+    "pose": (["enarf_pose.hip"], "enarf_pose.h"),          # the pose prior's bone masks
+    "photo": (["enarf_photo.hip"], "enarf_photo.h"),       # the photometric loss and image metrics of the single-scene path
+    "guide": (["enarf_guide.hip"], "enarf_guide.h"),       # the mask-guidance loss of the GAN's generator
+}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
          "-I", os.path.join(ROOT, "include"), "-I", CSRC]
+
+
+def lib_path(stem: str) -> str:
+    return os.path.join(CSRC, f"libenarf_{stem}.so")
+
+
+def binding(stem: str) -> str:
+    """name of the module that binds the row's library"""
+    return "enarf_gan_amd._lib" if stem == "hip" else f"enarf_gan_amd._{stem}_lib"
+
+
+def lib_deps(stem: str) -> list:
+    """What every object of the row depends on: every header next to the sources (a list by name went stale when
+    enarf_tasks.h was added), include/enarf_hip.h, the row's own public header and this file."""
+    include = os.path.join(ROOT, "include")
+    return ([os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h")] +
+            [os.path.join(include, "enarf_hip.h"), os.path.join(include, LIBRARIES[stem][1]), os.path.abspath(__file__)])
+
+
+LIB = lib_path("hip")
+# the names earlier callers use, all read from the table
+MESH_LIB, RASTER_LIB, POSE_LIB, PHOTO_LIB, GUIDE_LIB = (lib_path(s) for s in ("mesh", "raster", "pose", "photo", "guide"))
+SOURCES, HEADERS = LIBRARIES["hip"][0], lib_deps("hip")
 
 
 def _newer(a: str, b: str) -> bool:
     return (not os.path.exists(b)) or os.path.getmtime(a) > os.path.getmtime(b)
 
 
-def build(force: bool = False, verbose: bool = False, extra_flags=()) -> str:
-    """Build the six libraries incrementally; returns the path of libenarf_hip.so (MESH_LIB, RASTER_LIB, POSE_LIB,
-    PHOTO_LIB and GUIDE_LIB are next to it)."""
+def _make(targets, force, verbose, extra_flags) -> None:
+    """targets: (library, object directory, sources, dependencies) each; compiles what is out of date, then links"""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    deps = [os.path.join(CSRC, h) if not os.path.isabs(h) else h for h in HEADERS] + [os.path.abspath(__file__)]
     libs, jobs = [], []
-    for lib, sources, lib_deps in ((LIB, SOURCES, deps), (MESH_LIB, MESH_SOURCES, deps + MESH_HEADERS),
-                                   (RASTER_LIB, RASTER_SOURCES, deps + RASTER_HEADERS),
-                                   (POSE_LIB, POSE_SOURCES, deps + POSE_HEADERS),
-                                   (PHOTO_LIB, PHOTO_SOURCES, deps + PHOTO_HEADERS),
-                                   (GUIDE_LIB, GUIDE_SOURCES, deps + GUIDE_HEADERS)):
+    for lib, obj_dir, sources, deps in targets:
         objs, n_jobs = [], len(jobs)
         for src in sources:
             s = os.path.join(CSRC, src)
-            o = os.path.join(CSRC, src.replace(".hip", ".o"))
+            o = os.path.join(obj_dir, src.replace(".hip", ".o"))
             objs.append(o)
-            if force or _newer(s, o) or any(_newer(d, o) for d in lib_deps):
+            if force or _newer(s, o) or any(_newer(d, o) for d in deps):
                 jobs.append([hipcc, *FLAGS, *extra_flags, "-c", s, "-o", o])
         libs.append((lib, objs, len(jobs) > n_jobs))
 
@@ -75,15 +84,34 @@ def build(force: bool = False, verbose: bool = False, extra_flags=()) -> str:
         if verbose and r.stderr.strip():
             print(r.stderr, file=sys.stderr)
 
-    n_sources = (len(SOURCES) + len(MESH_SOURCES) + len(RASTER_SOURCES) + len(POSE_SOURCES) + len(PHOTO_SOURCES) +
-                 len(GUIDE_SOURCES))
-    with ThreadPoolExecutor(max_workers=n_sources) as ex:
+    with ThreadPoolExecutor(max_workers=sum(len(t[2]) for t in targets)) as ex:
         list(ex.map(run, jobs))
     for lib, objs, rebuilt in libs:
         if rebuilt or force or not os.path.exists(lib) or any(_newer(o, lib) for o in objs):
             run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib, *objs])
+
+
+def build(force: bool = False, verbose: bool = False, extra_flags=()) -> str:
+    """Build every library of LIBRARIES incrementally; returns the path of libenarf_hip.so (the others are next to it,
+    at lib_path(stem))."""
+    _make([(lib_path(stem), CSRC, sources, lib_deps(stem)) for stem, (sources, _) in LIBRARIES.items()],
+          force, verbose, extra_flags)
     return LIB
 
 
+def build_variant(name: str, extra_flags=()) -> str:
+    """A second build of the `hip` row with extra compiler flags: variants/libenarf_NAME.so, objects under
+    variants/obj_NAME/ (git-ignored; loaded through _lib.use_variant by the measurement tools)."""
+    out = os.path.join(ROOT, "variants")
+    os.makedirs(os.path.join(out, "obj_" + name), exist_ok=True)
+    lib = os.path.join(out, f"libenarf_{name}.so")
+    _make([(lib, os.path.join(out, "obj_" + name), LIBRARIES["hip"][0], lib_deps("hip"))], True, True, extra_flags)
+    return lib
+
+
 if __name__ == "__main__":
-    print(build(force="--force" in sys.argv, verbose=True))
+    if "--variant" in sys.argv:
+        at = sys.argv.index("--variant")
+        print(build_variant(sys.argv[at + 1], sys.argv[at + 2:]))
+    else:
+        print(build(force="--force" in sys.argv, verbose=True))

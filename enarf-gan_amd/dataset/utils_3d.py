@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from .. import _pose_lib
-from .._lib import EnarfHipError
+from .._loader import EnarfHipError, stream_of
 
 # add_blank_part's joint list, and the first position of each of the 24 original joints in it
 BLANK_IDX = [0, 0] + list(range(10)) + [9, 9] + list(range(10, 24))
@@ -79,10 +79,9 @@ def create_mask(hpp, joint_mat_camera, joint_pos_image, size, thickness=1.5):
         out = {"mask": torch.empty(1, S, S, device=dev), "disparity": torch.empty(1, S, S, device=dev),
                "part_disparity": torch.empty(1, _pose_lib.NUM_PARTS, S, S, device=dev),
                "keypoint_mask": torch.empty(1, _pose_lib.NUM_KEYPOINTS, S, S, device=dev)}
-        stream = torch.cuda.current_stream(dev).cuda_stream
         _pose_lib.check(lib.enarf_pose_bone_masks(pose.data_ptr(), None, jpos.data_ptr(), 1, S, float(thickness),
                                                   out["mask"].data_ptr(), out["disparity"].data_ptr(),
                                                   out["part_disparity"].data_ptr(), out["keypoint_mask"].data_ptr(),
-                                                  None, stream), "enarf_pose_bone_masks")
+                                                  None, stream_of(dev)), "enarf_pose_bone_masks")
     res = (out["disparity"][0], out["mask"][0], out["part_disparity"][0], out["keypoint_mask"][0])
     return res if on_device else tuple(r.cpu().numpy() for r in res)

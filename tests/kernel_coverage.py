@@ -1,8 +1,9 @@
-"""Which GPU tests launch each kernel instantiation of libenarf_hip.so and compare its output with a reference.
+"""Which GPU tests launch each kernel instantiation of each HIP library and compare its output with a reference.
 
+One map per row of enarf_gan_amd.build.LIBRARIES (LIBRARY_KERNEL_TESTS at the end; KERNEL_TESTS is libenarf_hip.so's).
 Keys: every instantiation the library builds, demangled as its `.kd` (kernel descriptor) symbol prints
 (tools/check_mfma_chains.kernel_symbols); values: `module::function` of tests under tests/. A kernel-trace run of the GPU
-suite (rocprofv3 --kernel-trace) is what these entries were read from. tests/test_kernel_coverage_cpu.py requires the keys to
+suite (rocprofv3 --kernel-trace) is what these entries were read from. tests/test_libraries_cpu.py requires the keys to
 equal the built set, every entry to be non-empty and every named test to exist: a new template instantiation needs a test
 named here before the CPU suite passes.
 """
@@ -170,3 +171,105 @@ KERNEL_TESTS = {
         "test_gpu_backward::test_render_backward_matches_oracle_autograd", "test_gpu_backward::test_query_backward_matches_oracle_autograd",
         "test_gpu_backward_f64::test_prepare_bwd_vs_float64"],
 }
+
+# ---- libenarf_mesh.so
+MESH_KERNEL_TESTS = {
+    "(anonymous namespace)::mc_count_kernel(float const*, int, int, int, float, int*, int*, long long*, long long*, long long)": [
+        "test_gpu_mesh::test_marching_cubes_matches_reference",
+        "test_gpu_mesh::test_667_cube_counts_match_torch",
+    ],
+    "(anonymous namespace)::mc_scan_kernel(long long*, long long*, long long, long*, long long*)": [
+        "test_gpu_mesh::test_marching_cubes_matches_reference",
+        "test_gpu_mesh::test_667_cube_counts_match_torch",
+    ],
+    "(anonymous namespace)::mc_emit_kernel(float const*, int, int, int, float, int const*, int const*, long long const*, long long const*, long long const*, float*, long*)": [
+        "test_gpu_mesh::test_marching_cubes_matches_reference",
+        "test_gpu_mesh::test_closed_surfaces_are_watertight_and_deterministic",
+        "test_gpu_mesh::test_667_cube_counts_match_torch",
+    ],
+}
+
+# ---- libenarf_raster.so
+_PROJ = "HIP_vector_type<double, 2u> const*, float const*"
+RASTER_KERNEL_TESTS = {
+    "(anonymous namespace)::raster_project_kernel(float const*, long long, float const*, double, HIP_vector_type<double, 2u>*, float*)": [
+        "test_gpu_raster::test_hand_placed_triangles_match_reference",
+        "test_gpu_raster::test_marching_cubes_meshes_match_reference",
+    ],
+    f"(anonymous namespace)::raster_depth_kernel(long const*, long long, long long, {_PROJ}, int, unsigned long long*, int*, int*)": [
+        "test_gpu_raster::test_hand_placed_triangles_match_reference",
+        "test_gpu_raster::test_marching_cubes_meshes_match_reference",
+    ],
+    f"(anonymous namespace)::raster_big_kernel(long const*, long long, {_PROJ}, int, unsigned long long*, int const*, int const*)": [
+        "test_gpu_raster::test_hand_placed_triangles_match_reference",
+        "test_gpu_raster::test_screen_filling_triangles_match_reference",
+    ],
+    "(anonymous namespace)::raster_mark_kernel(unsigned long long const*, long long, long const*, int*, int*, int*, long long)": [
+        "test_gpu_raster::test_hand_placed_triangles_match_reference",
+        "test_gpu_raster::test_marching_cubes_meshes_match_reference",
+    ],
+    "(anonymous namespace)::raster_count_kernel(long const*, long long, long long, int const*, int*)": [
+        "test_gpu_raster::test_marching_cubes_meshes_match_reference",
+    ],
+    "(anonymous namespace)::raster_scan_kernel(int const*, int const*, long long, long long*)": [
+        "test_gpu_raster::test_marching_cubes_meshes_match_reference",
+    ],
+    "(anonymous namespace)::raster_fill_kernel(long const*, long long, long long, int const*, int*, long long const*, int*)": [
+        "test_gpu_raster::test_marching_cubes_meshes_match_reference",
+    ],
+    "(anonymous namespace)::raster_vnormal_kernel(float const*, long const*, int const*, long long, long long const*, int*, double*)": [
+        "test_gpu_raster::test_marching_cubes_meshes_match_reference",
+        "test_gpu_raster::test_hand_placed_triangles_match_reference",
+    ],
+    f"(anonymous namespace)::raster_shade_kernel(unsigned long long const*, int, long const*, long long, float const*, {_PROJ}, int const*, double const*, unsigned char*, long*, float*, float*, float*)": [
+        "test_gpu_raster::test_hand_placed_triangles_match_reference",
+        "test_gpu_raster::test_marching_cubes_meshes_match_reference",
+        "test_gpu_raster::test_empty_mesh_is_all_background",
+    ],
+}
+
+# ---- libenarf_pose.so
+_POSE_ARGS = "(anonymous namespace)::Args"
+POSE_KERNEL_TESTS = {
+    f"void (anonymous namespace)::pose_mask_kernel<{d}, {k}>({_POSE_ARGS})": tests
+    for (d, k), tests in {
+        ("true", "true"): ["test_gpu_pose::test_kernel_matches_restatement_bit_for_bit",
+                           "test_gpu_pose::test_edge_cases_match_restatement",
+                           "test_gpu_pose::test_kernel_matches_reference_goldens"],
+        ("true", "false"): ["test_gpu_pose::test_null_outputs_are_not_written"],
+        ("false", "true"): ["test_gpu_pose::test_null_outputs_are_not_written"],
+        ("false", "false"): ["test_gpu_pose::test_kernel_matches_restatement_bit_for_bit",
+                             "test_gpu_pose::test_dataset_batches_reproduce_reference_items"],
+    }.items()
+}
+
+# ---- libenarf_photo.so
+_NS = "(anonymous namespace)::"
+_LOSS_TESTS = ["test_gpu_photo::test_loss_matches_restatement", "test_gpu_photo::test_loss_matches_reference_fixture",
+               "test_gpu_photo::test_two_runs_give_identical_bits"]
+_METRIC_TESTS = ["test_gpu_photo::test_metrics_match_restatement", "test_gpu_photo::test_metrics_rectangles",
+                 "test_gpu_photo::test_two_runs_give_identical_bits"]
+PHOTO_KERNEL_TESTS = {
+    f"{_NS}photo_loss_kernel({_NS}LossArgs, double*)": _LOSS_TESTS,
+    f"{_NS}photo_loss_finish_kernel(double const*, int, double, double, double, double, int, float*)": _LOSS_TESTS,
+    f"{_NS}photo_loss_bwd_kernel({_NS}LossArgs, float const*, float const*, float*, float*)": _LOSS_TESTS,
+    f"{_NS}photo_metrics_kernel({_NS}MetricArgs, double*)": _METRIC_TESTS,
+    f"{_NS}photo_metrics_finish_kernel({_NS}MetricArgs, double const*, float*)": _METRIC_TESTS,
+}
+
+# ---- libenarf_guide.so (guide_hist_kernel is launched only when the push term is on: each of its tests runs a ratio > 0)
+_GUIDE_TESTS = ["test_gpu_mask_guidance::test_fixture_cases_match_reference_and_referee",
+                "test_gpu_mask_guidance::test_training_sizes_match_referee_and_are_no_further_from_it_than_torch",
+                "test_gpu_mask_guidance::test_two_runs_give_identical_bits"]
+GUIDE_KERNEL_TESTS = {
+    f"{_NS}guide_hist_kernel({_NS}Args, int, {_NS}Work*)": _GUIDE_TESTS,
+    f"{_NS}guide_sum_kernel({_NS}Args, {_NS}Work*, int*)": _GUIDE_TESTS,
+    f"{_NS}guide_finish_kernel({_NS}Args, int, {_NS}Work const*, int*, float*)": _GUIDE_TESTS,
+    f"{_NS}guide_bwd_kernel({_NS}Args, int const*, float const*, float*)": _GUIDE_TESTS,
+}
+
+# one map per row of enarf_gan_amd.build.LIBRARIES, and the one GPU test module the side libraries' entries name
+LIBRARY_KERNEL_TESTS = {"hip": KERNEL_TESTS, "mesh": MESH_KERNEL_TESTS, "raster": RASTER_KERNEL_TESTS, "pose": POSE_KERNEL_TESTS,
+                        "photo": PHOTO_KERNEL_TESTS, "guide": GUIDE_KERNEL_TESTS}
+GPU_TEST_MODULE = {"mesh": "test_gpu_mesh", "raster": "test_gpu_raster", "pose": "test_gpu_pose", "photo": "test_gpu_photo",
+                   "guide": "test_gpu_mask_guidance"}

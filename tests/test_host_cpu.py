@@ -2,33 +2,22 @@
 argument validation works without touching a device, and the Python mirror keeps the reference's names."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import libraries as L
 
-
-def _declared_functions():
-    src = open(os.path.join(ROOT, "include", "enarf_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    names = re.findall(r"\b(enarf_[a-z0-9_]+)\s*\(", src)
-    return sorted(set(names))
+ROOT = L.ROOT
 
 
 def test_header_symbols_all_exported_and_bound():
+    """what is specific to libenarf_hip.so; tests/test_libraries_cpu.py holds the checks every library gets"""
     from enarf_gan_amd import _lib
-    lib = _lib.load()
-    declared = _declared_functions()
-    assert len(declared) >= 11
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in enarf_hip.h but not exported by libenarf_hip.so"
-        assert name in _lib.SIGNATURES, f"{name} has no ctypes signature in _lib.py"
-    assert set(_lib.SIGNATURES) == set(declared)
-    assert lib.enarf_abi_version() == _lib.ABI_VERSION == 4
-    assert lib.enarf_mlp_pack_bytes() % 16 == 0
+    assert len(L.declared("hip")) >= 11
+    assert _lib.ABI_VERSION == 4
+    assert _lib.load().enarf_mlp_pack_bytes() % 16 == 0
 
 
 def test_struct_layouts_match_the_header():
@@ -106,33 +95,11 @@ def test_tap_offsets_stay_inside_the_plane(tmp_path):
     assert int(r.stdout.split()[1]) > 100000
 
 
-def test_build_tracks_every_included_header():
-    """enarf_gan_amd.build rebuilds an object when any header its source includes (directly or through another header)
-    changed: a header missing from the dependency list leaves the product library stale after a header-only edit."""
-    import re
-    from enarf_gan_amd import build as B
-    tracked = {os.path.basename(h) for h in B.HEADERS}
-    seen, todo = set(), list(B.SOURCES)
-    while todo:
-        f = todo.pop()
-        path = os.path.join(B.CSRC, f) if os.path.exists(os.path.join(B.CSRC, f)) else os.path.join(ROOT, "include", f)
-        for inc in re.findall(r'#include\s+"([^"]+)"', open(path).read()):
-            if inc not in seen:
-                seen.add(inc)
-                todo.append(inc)
-    assert seen and seen <= tracked, seen - tracked
-
-
 def test_built_library_has_only_in_place_mfma_chains():
     """ISA lint of the built library (tools/check_mfma_chains.py): a chained MFMA whose vDst differs from its SrcC, or
     partially overlaps it, is issued by the compiler without a wait state and does not reliably see its predecessor's
     result on gfx950 - the cause of the round-1 renderer's run-to-run differences in the split-precision MLP modes."""
-    import importlib.util
-    from enarf_gan_amd import build
-    spec = importlib.util.spec_from_file_location("check_mfma_chains", os.path.join(ROOT, "tools", "check_mfma_chains.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    kernels, n_mfma, problems = mod.check(build.LIB)
+    kernels, n_mfma, problems = L.tool("check_mfma_chains").check(L.library("hip"))
     assert n_mfma > 1000 and kernels > 20
     assert not problems, problems[:5]
 

@@ -1,8 +1,6 @@
 """CPU checks of the GAN supervision (libenarf_guide.so, include/enarf_guide.h): the float64 restatement
 (tests/mask_guidance_reference.py) against the reference's recorded losses and gradients and against the torch functions
 of models/loss.py, the library's ABI and kernel inventory, and the refusals that need no device."""
-import ctypes as C
-import importlib.util
 import os
 import re
 
@@ -10,35 +8,12 @@ import numpy as np
 import pytest
 import torch
 
+import libraries as L
 import mask_guidance_reference as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TESTS = os.path.join(ROOT, "tests")
+ROOT, TESTS = L.ROOT, L.TESTS
 SRC = os.path.join(ROOT, "enarf-gan_amd", "csrc", "enarf_guide.hip")
-HEADER = os.path.join(ROOT, "include", "enarf_guide.h")
-
-_NS = "(anonymous namespace)::"
-GUIDE_KERNELS = {
-    f"{_NS}guide_hist_kernel({_NS}Args, int, {_NS}Work*)",
-    f"{_NS}guide_sum_kernel({_NS}Args, {_NS}Work*, int*)",
-    f"{_NS}guide_finish_kernel({_NS}Args, int, {_NS}Work const*, int*, float*)",
-    f"{_NS}guide_bwd_kernel({_NS}Args, int const*, float const*, float*)",
-}
-
-
-def _tool(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tools", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-@pytest.fixture(scope="module")
-def guide_library():
-    from enarf_gan_amd import build
-    build.build()
-    return build.GUIDE_LIB
-
+HEADER = L.header("guide")
 
 def golden():
     return np.load(os.path.join(TESTS, "golden", "mask_guidance.npz"))
@@ -131,22 +106,13 @@ def test_restatement_key_order_and_pooling():
 
 
 # ------------------------------------------------------------------------------------------------- the library
-def _declared():
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(enarf_guide_[a-z0-9_]+)\s*\(", src)))
-
-
-def test_header_symbols_exported_and_bound(guide_library):
+def test_header_symbols_exported_and_bound():
+    """what is specific to this library; tests/test_libraries_cpu.py holds the checks every library gets"""
     from enarf_gan_amd import _guide_lib
-    lib = C.CDLL(guide_library)
-    declared = _declared()
-    assert declared == ["enarf_guide_abi_version", "enarf_guide_last_error", "enarf_guide_loss_bwd", "enarf_guide_loss_fwd"]
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in enarf_guide.h but not exported by libenarf_guide.so"
-    assert set(_guide_lib.SIGNATURES) == set(declared)
-    assert _guide_lib.load().enarf_guide_abi_version() == _guide_lib.ABI_VERSION == 1
+    assert L.declared("guide") == ["enarf_guide_abi_version", "enarf_guide_last_error", "enarf_guide_loss_bwd",
+                                   "enarf_guide_loss_fwd"]
+    assert _guide_lib.ABI_VERSION == 1
     header = open(HEADER).read()
-    assert "#define ENARF_GUIDE_ABI_VERSION 1" in header
     assert f"#define ENARF_GUIDE_MAX_BLOCKS {_guide_lib.MAX_BLOCKS}" in header
     assert "#define ENARF_GUIDE_RADIX_BITS 8" in header and "#define ENARF_GUIDE_PASSES     4" in header
     assert _guide_lib.WORK_BYTES == 2 * 512 * 8 + (4 * 256 + 2 * 512) * 4 and _guide_lib.STATE_INTS == 4 + 512
@@ -155,15 +121,6 @@ def test_header_symbols_exported_and_bound(guide_library):
     for n in (1, 255, 256, 1000, 131072, 131073, (1 << 31) - 1):
         chunk_len, chunks = _guide_lib.geometry(n)
         assert chunk_len % 256 == 0 and chunks <= _guide_lib.MAX_BLOCKS and (chunks - 1) * chunk_len < n <= chunks * chunk_len
-
-
-def test_guide_kernels_are_a_library_of_their_own(guide_library):
-    from enarf_gan_amd import build
-    chains = _tool("check_mfma_chains")
-    built = set(chains.kernel_symbols(guide_library))
-    assert built == GUIDE_KERNELS, sorted(built ^ GUIDE_KERNELS)
-    for other in (build.LIB, build.MESH_LIB, build.RASTER_LIB, build.POSE_LIB, build.PHOTO_LIB):
-        assert not built & set(chains.kernel_symbols(other)), f"a guide kernel inside {other}"
 
 
 def test_sources_read_no_environment_and_hold_no_assembly_or_float_atomics():
@@ -178,8 +135,9 @@ def test_sources_read_no_environment_and_hold_no_assembly_or_float_atomics():
         assert "os.environ" not in text and "getenv" not in text, path
 
 
-def test_abi_refusals_need_no_device(guide_library):
+def test_abi_refusals_need_no_device():
     from enarf_gan_amd import _guide_lib
+    L.library("guide")
     lib = _guide_lib.load()
     err = lib.enarf_guide_last_error
 
@@ -201,7 +159,7 @@ def test_abi_refusals_need_no_device(guide_library):
     assert bwd(state=None) == -1 and bwd(up=None) == -1 and bwd(d=None) == -1
 
 
-def test_binding_refusals_need_no_device(guide_library):
+def test_binding_refusals_need_no_device():
     from enarf_gan_amd import ops
     from enarf_gan_amd._lib import EnarfHipError
     from enarf_gan_amd.models.loss import mask_guidance_loss

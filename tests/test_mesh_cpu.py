@@ -1,12 +1,8 @@
 """CPU checks of marching cubes (libenarf_mesh.so, include/enarf_mesh.h): the generated case table and its rule, the
 numpy restatement of the contract (tests/mc_reference.py) on closed fields, the library's exported ABI and kernel
 inventory, and the host layer's refusals without a device."""
-import ast
-import ctypes as C
-import importlib.util
 import math
 import os
-import re
 import subprocess
 import sys
 
@@ -14,44 +10,10 @@ import numpy as np
 import pytest
 import torch
 
+import libraries as L
 import mc_reference as M
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TESTS = os.path.join(ROOT, "tests")
-
-# every kernel of libenarf_mesh.so -> GPU tests that launch it and compare with a reference (the rule
-# test_kernel_coverage_cpu.py applies to libenarf_hip.so)
-MESH_KERNEL_TESTS = {
-    "(anonymous namespace)::mc_count_kernel(float const*, int, int, int, float, int*, int*, long long*, long long*, long long)": [
-        "test_gpu_mesh::test_marching_cubes_matches_reference",
-        "test_gpu_mesh::test_667_cube_counts_match_torch",
-    ],
-    "(anonymous namespace)::mc_scan_kernel(long long*, long long*, long long, long*, long long*)": [
-        "test_gpu_mesh::test_marching_cubes_matches_reference",
-        "test_gpu_mesh::test_667_cube_counts_match_torch",
-    ],
-    "(anonymous namespace)::mc_emit_kernel(float const*, int, int, int, float, int const*, int const*, long long const*, long long const*, long long const*, float*, long*)": [
-        "test_gpu_mesh::test_marching_cubes_matches_reference",
-        "test_gpu_mesh::test_closed_surfaces_are_watertight_and_deterministic",
-        "test_gpu_mesh::test_667_cube_counts_match_torch",
-    ],
-}
-
-
-def _tool(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tools", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-@pytest.fixture(scope="module")
-def mesh_library():
-    """build() is incremental: it builds libenarf_mesh.so next to libenarf_hip.so if this checkout has not yet"""
-    from enarf_gan_amd import build
-    build.build()
-    return build.MESH_LIB
-
+ROOT = L.ROOT
 
 # ------------------------------------------------------------------------------------------------- the table
 def test_generator_reproduces_the_committed_header():
@@ -153,41 +115,16 @@ def test_reference_topology_and_volume():
 
 
 # ------------------------------------------------------------------------------------------------- the library
-def _declared():
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "enarf_mesh.h")).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(enarf_mesh_[a-z0-9_]+)\s*\(", src)))
-
-
-def test_header_symbols_exported_and_bound(mesh_library):
+def test_header_symbols_exported_and_bound():
+    """what is specific to this library; tests/test_libraries_cpu.py holds the checks every library gets"""
     from enarf_gan_amd import _mesh_lib
-    lib = C.CDLL(mesh_library)
-    declared = _declared()
-    assert len(declared) == 5
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in enarf_mesh.h but not exported by libenarf_mesh.so"
-    assert set(_mesh_lib.SIGNATURES) == set(declared)
-    assert _mesh_lib.load().enarf_mesh_abi_version() == _mesh_lib.ABI_VERSION == 1
-    h = open(os.path.join(ROOT, "include", "enarf_mesh.h")).read()
-    assert "#define ENARF_MESH_ABI_VERSION 1" in h
+    assert len(L.declared("mesh")) == 5
+    assert _mesh_lib.ABI_VERSION == 1
 
 
-def test_mesh_kernels_are_separate_and_each_has_gpu_tests(mesh_library):
-    from enarf_gan_amd import build
-    chains = _tool("check_mfma_chains")
-    built = set(chains.kernel_symbols(mesh_library))
-    assert built == set(MESH_KERNEL_TESTS), sorted(built ^ set(MESH_KERNEL_TESTS))
-    assert not built & set(chains.kernel_symbols(build.LIB)), "a marching-cubes kernel inside libenarf_hip.so"
-    tree = ast.parse(open(os.path.join(TESTS, "test_gpu_mesh.py")).read())
-    functions = {n.name for n in tree.body if isinstance(n, ast.FunctionDef)}
-    for kernel, tests in MESH_KERNEL_TESTS.items():
-        assert tests, kernel
-        for t in tests:
-            module, func = t.split("::")
-            assert module == "test_gpu_mesh" and func in functions, f"{kernel}: {t} does not exist"
-
-
-def test_argument_checks_need_no_device(mesh_library):
+def test_argument_checks_need_no_device():
     from enarf_gan_amd import _mesh_lib
+    L.library("mesh")
     lib = _mesh_lib.load()
     assert lib.enarf_mesh_workspace_bytes(1, 5, 5) == 0
     assert lib.enarf_mesh_workspace_bytes(2048, 1024, 1024) == 0           # 2^31 points
@@ -199,7 +136,7 @@ def test_argument_checks_need_no_device(mesh_library):
     assert lib.enarf_mesh_emit(None, 4, 1, 4, 0.0, None, None, None, None) == -1
 
 
-def test_host_layer_has_no_cpu_fallback(mesh_library):
+def test_host_layer_has_no_cpu_fallback():
     from enarf_gan_amd._lib import EnarfHipError
     from enarf_gan_amd.libraries.NARF.mesh_rendering import extract_mesh, marching_cubes
     with pytest.raises(EnarfHipError):

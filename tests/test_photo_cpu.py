@@ -1,52 +1,20 @@
 """CPU checks of the DSO supervision (libenarf_photo.so, include/enarf_photo.h): the float64 restatement
 (tests/photo_reference.py) against the reference's recorded losses and gradients and against the properties that pin its
 SSIM, the library's ABI and kernel inventory, and the argument checks that need no device."""
-import ast
 import ctypes as C
-import importlib.util
 import os
-import re
 import types
 
 import numpy as np
 import pytest
 import torch
 
+import libraries as L
 import photo_reference as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TESTS = os.path.join(ROOT, "tests")
+ROOT, TESTS = L.ROOT, L.TESTS
 SRC = os.path.join(ROOT, "enarf-gan_amd", "csrc", "enarf_photo.hip")
-HEADER = os.path.join(ROOT, "include", "enarf_photo.h")
-
-_NS = "(anonymous namespace)::"
-_LOSS_TESTS = ["test_gpu_photo::test_loss_matches_restatement", "test_gpu_photo::test_loss_matches_reference_fixture",
-               "test_gpu_photo::test_two_runs_give_identical_bits"]
-_METRIC_TESTS = ["test_gpu_photo::test_metrics_match_restatement", "test_gpu_photo::test_metrics_rectangles",
-                 "test_gpu_photo::test_two_runs_give_identical_bits"]
-# every kernel of libenarf_photo.so -> GPU tests that launch it and compare with the restatement
-PHOTO_KERNEL_TESTS = {
-    f"{_NS}photo_loss_kernel({_NS}LossArgs, double*)": _LOSS_TESTS,
-    f"{_NS}photo_loss_finish_kernel(double const*, int, double, double, double, double, int, float*)": _LOSS_TESTS,
-    f"{_NS}photo_loss_bwd_kernel({_NS}LossArgs, float const*, float const*, float*, float*)": _LOSS_TESTS,
-    f"{_NS}photo_metrics_kernel({_NS}MetricArgs, double*)": _METRIC_TESTS,
-    f"{_NS}photo_metrics_finish_kernel({_NS}MetricArgs, double const*, float*)": _METRIC_TESTS,
-}
-
-
-def _tool(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tools", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-@pytest.fixture(scope="module")
-def photo_library():
-    from enarf_gan_amd import build
-    build.build()
-    return build.PHOTO_LIB
-
+HEADER = L.header("photo")
 
 def golden():
     return np.load(os.path.join(TESTS, "golden", "photometric.npz"))
@@ -137,44 +105,18 @@ def test_ssim_properties_pin_the_restatement():
 
 
 # ------------------------------------------------------------------------------------------------- the library
-def _declared():
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(enarf_photo_[a-z0-9_]+)\s*\(", src)))
-
-
-def test_header_symbols_exported_and_bound(photo_library):
+def test_header_symbols_exported_and_bound():
+    """what is specific to this library; tests/test_libraries_cpu.py holds the checks every library gets"""
     from enarf_gan_amd import _photo_lib
-    lib = C.CDLL(photo_library)
-    declared = _declared()
-    assert declared == ["enarf_photo_abi_version", "enarf_photo_last_error", "enarf_photo_loss_bwd",
-                        "enarf_photo_loss_fwd", "enarf_photo_metrics"]
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in enarf_photo.h but not exported by libenarf_photo.so"
-    assert set(_photo_lib.SIGNATURES) == set(declared)
-    assert _photo_lib.load().enarf_photo_abi_version() == _photo_lib.ABI_VERSION == 1
+    assert L.declared("photo") == ["enarf_photo_abi_version", "enarf_photo_last_error", "enarf_photo_loss_bwd",
+                                   "enarf_photo_loss_fwd", "enarf_photo_metrics"]
+    assert _photo_lib.ABI_VERSION == 1
     header = open(HEADER).read()
-    assert "#define ENARF_PHOTO_ABI_VERSION 1" in header
     assert "#define ENARF_PHOTO_LOSS_MAX_BLOCKS 1024" in header and _photo_lib.LOSS_PARTIALS == 2048
     assert f"#define ENARF_PHOTO_TILE     {_photo_lib.TILE}" in header
     assert f"#define ENARF_PHOTO_WINDOW   {_photo_lib.WINDOW}" in header
     assert f"#define ENARF_PHOTO_MAE_THRESHOLD {_photo_lib.MAE_THRESHOLD}" in header and R.MAE_THRESHOLD == 0.01
     assert _photo_lib.metric_partials(17, 512) == 3 * 2 * 32
-
-
-def test_photo_kernels_are_separate_and_each_has_gpu_tests(photo_library):
-    from enarf_gan_amd import build
-    chains = _tool("check_mfma_chains")
-    built = set(chains.kernel_symbols(photo_library))
-    assert built == set(PHOTO_KERNEL_TESTS), sorted(built ^ set(PHOTO_KERNEL_TESTS))
-    for other in (build.LIB, build.MESH_LIB, build.RASTER_LIB, build.POSE_LIB):
-        assert not built & set(chains.kernel_symbols(other)), f"a photo kernel inside {other}"
-    tree = ast.parse(open(os.path.join(TESTS, "test_gpu_photo.py")).read())
-    functions = {n.name for n in tree.body if isinstance(n, ast.FunctionDef)}
-    for kernel, tests in PHOTO_KERNEL_TESTS.items():
-        assert tests, kernel
-        for t in tests:
-            module, func = t.split("::")
-            assert module == "test_gpu_photo" and func in functions, f"{kernel}: {t} does not exist"
 
 
 def test_sources_read_no_environment_and_hold_no_assembly():
@@ -187,8 +129,9 @@ def test_sources_read_no_environment_and_hold_no_assembly():
         assert "os.environ" not in src and "getenv" not in src, path
 
 
-def test_abi_argument_checks_need_no_device(photo_library):
+def test_abi_argument_checks_need_no_device():
     from enarf_gan_amd import _photo_lib
+    L.library("photo")
     lib = _photo_lib.load()
     err = lib.enarf_photo_last_error
 
@@ -222,7 +165,7 @@ def test_abi_argument_checks_need_no_device(photo_library):
     assert metrics(B=0) == 0
 
 
-def test_binding_argument_checks_need_no_device(photo_library):
+def test_binding_argument_checks_need_no_device():
     from enarf_gan_amd import ops
     from enarf_gan_amd._lib import EnarfHipError
     from enarf_gan_amd.libraries import metrics as M

@@ -1,9 +1,6 @@
 """CPU checks of the pose prior's bone masks (libenarf_pose.so, include/enarf_pose.h): the numpy restatement of the
 contract (tests/bone_mask_reference.py) against the reference's recorded outputs, the hard-coded SMPL tables, the
 library's ABI and kernel inventory, the argument checks, the pose-only cache reader and the batch order."""
-import ast
-import ctypes as C
-import importlib.util
 import os
 import pickle
 import re
@@ -13,41 +10,11 @@ import pytest
 import torch
 
 import bone_mask_reference as R
+import libraries as L
 import pose_golden as PG
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TESTS = os.path.join(ROOT, "tests")
+ROOT = L.ROOT
 SRC = os.path.join(ROOT, "enarf-gan_amd", "csrc", "enarf_pose.hip")
-
-_ARGS = "(anonymous namespace)::Args"
-# every kernel of libenarf_pose.so -> GPU tests that launch it and compare with the restatement
-POSE_KERNEL_TESTS = {
-    f"void (anonymous namespace)::pose_mask_kernel<{d}, {k}>({_ARGS})": tests
-    for (d, k), tests in {
-        ("true", "true"): ["test_gpu_pose::test_kernel_matches_restatement_bit_for_bit",
-                           "test_gpu_pose::test_edge_cases_match_restatement",
-                           "test_gpu_pose::test_kernel_matches_reference_goldens"],
-        ("true", "false"): ["test_gpu_pose::test_null_outputs_are_not_written"],
-        ("false", "true"): ["test_gpu_pose::test_null_outputs_are_not_written"],
-        ("false", "false"): ["test_gpu_pose::test_kernel_matches_restatement_bit_for_bit",
-                             "test_gpu_pose::test_dataset_batches_reproduce_reference_items"],
-    }.items()
-}
-
-
-def _tool(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tools", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-@pytest.fixture(scope="module")
-def pose_library():
-    from enarf_gan_amd import build
-    build.build()
-    return build.POSE_LIB
-
 
 # ------------------------------------------------------------------------------------------------- the restatement
 def test_restatement_reproduces_reference_goldens():
@@ -115,37 +82,11 @@ def test_smpl_tables_equal_recorded_ones():
 
 
 # ------------------------------------------------------------------------------------------------- the library
-def _declared():
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "enarf_pose.h")).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(enarf_pose_[a-z0-9_]+)\s*\(", src)))
-
-
-def test_header_symbols_exported_and_bound(pose_library):
+def test_header_symbols_exported_and_bound():
+    """what is specific to this library; tests/test_libraries_cpu.py holds the checks every library gets"""
     from enarf_gan_amd import _pose_lib
-    lib = C.CDLL(pose_library)
-    declared = _declared()
-    assert declared == ["enarf_pose_abi_version", "enarf_pose_bone_masks", "enarf_pose_last_error"]
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in enarf_pose.h but not exported by libenarf_pose.so"
-    assert set(_pose_lib.SIGNATURES) == set(declared)
-    assert _pose_lib.load().enarf_pose_abi_version() == _pose_lib.ABI_VERSION == 1
-    assert "#define ENARF_POSE_ABI_VERSION 1" in open(os.path.join(ROOT, "include", "enarf_pose.h")).read()
-
-
-def test_pose_kernels_are_separate_and_each_has_gpu_tests(pose_library):
-    from enarf_gan_amd import build
-    chains = _tool("check_mfma_chains")
-    built = set(chains.kernel_symbols(pose_library))
-    assert built == set(POSE_KERNEL_TESTS), sorted(built ^ set(POSE_KERNEL_TESTS))
-    for other in (build.LIB, build.MESH_LIB, build.RASTER_LIB):
-        assert not built & set(chains.kernel_symbols(other)), f"a pose kernel inside {other}"
-    tree = ast.parse(open(os.path.join(TESTS, "test_gpu_pose.py")).read())
-    functions = {n.name for n in tree.body if isinstance(n, ast.FunctionDef)}
-    for kernel, tests in POSE_KERNEL_TESTS.items():
-        assert tests, kernel
-        for t in tests:
-            module, func = t.split("::")
-            assert module == "test_gpu_pose" and func in functions, f"{kernel}: {t} does not exist"
+    assert L.declared("pose") == ["enarf_pose_abi_version", "enarf_pose_bone_masks", "enarf_pose_last_error"]
+    assert _pose_lib.ABI_VERSION == 1
 
 
 def test_sources_read_no_environment_and_hold_no_assembly():
@@ -157,8 +98,9 @@ def test_sources_read_no_environment_and_hold_no_assembly():
         assert "os.environ" not in src and "getenv" not in src, path
 
 
-def test_argument_checks_need_no_device(pose_library):
+def test_argument_checks_need_no_device():
     from enarf_gan_amd import _pose_lib
+    L.library("pose")
     lib = _pose_lib.load()
     f = lib.enarf_pose_bone_masks
 
@@ -177,7 +119,7 @@ def test_argument_checks_need_no_device(pose_library):
     assert call(B=0, pose=None, K=None, mask=None) == 0
 
 
-def test_host_layer_has_no_cpu_fallback(pose_library):
+def test_host_layer_has_no_cpu_fallback():
     from enarf_gan_amd._lib import EnarfHipError
     from enarf_gan_amd.dataset.dataset import SMPLProperty
     from enarf_gan_amd.dataset.utils_3d import bone_masks, create_mask

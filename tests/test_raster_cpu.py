@@ -1,78 +1,18 @@
 """CPU checks of the mesh rasteriser (libenarf_raster.so, include/enarf_raster.h): the numpy restatement of the contract
 (tests/raster_reference.py) on hand-computed cases, the library's exported ABI and kernel inventory, and the host
 layer's refusals without a device."""
-import ast
-import ctypes as C
-import importlib.util
 import math
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import libraries as L
 import mc_reference as M
 import raster_reference as RR
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TESTS = os.path.join(ROOT, "tests")
-
-_PROJ = "HIP_vector_type<double, 2u> const*, float const*"
-# every kernel of libenarf_raster.so -> GPU tests that launch it and compare with the reference (the rule
-# test_kernel_coverage_cpu.py applies to libenarf_hip.so)
-RASTER_KERNEL_TESTS = {
-    "(anonymous namespace)::raster_project_kernel(float const*, long long, float const*, double, HIP_vector_type<double, 2u>*, float*)": [
-        "test_gpu_raster::test_hand_placed_triangles_match_reference",
-        "test_gpu_raster::test_marching_cubes_meshes_match_reference",
-    ],
-    f"(anonymous namespace)::raster_depth_kernel(long const*, long long, long long, {_PROJ}, int, unsigned long long*, int*, int*)": [
-        "test_gpu_raster::test_hand_placed_triangles_match_reference",
-        "test_gpu_raster::test_marching_cubes_meshes_match_reference",
-    ],
-    f"(anonymous namespace)::raster_big_kernel(long const*, long long, {_PROJ}, int, unsigned long long*, int const*, int const*)": [
-        "test_gpu_raster::test_hand_placed_triangles_match_reference",
-        "test_gpu_raster::test_screen_filling_triangles_match_reference",
-    ],
-    "(anonymous namespace)::raster_mark_kernel(unsigned long long const*, long long, long const*, int*, int*, int*, long long)": [
-        "test_gpu_raster::test_hand_placed_triangles_match_reference",
-        "test_gpu_raster::test_marching_cubes_meshes_match_reference",
-    ],
-    "(anonymous namespace)::raster_count_kernel(long const*, long long, long long, int const*, int*)": [
-        "test_gpu_raster::test_marching_cubes_meshes_match_reference",
-    ],
-    "(anonymous namespace)::raster_scan_kernel(int const*, int const*, long long, long long*)": [
-        "test_gpu_raster::test_marching_cubes_meshes_match_reference",
-    ],
-    "(anonymous namespace)::raster_fill_kernel(long const*, long long, long long, int const*, int*, long long const*, int*)": [
-        "test_gpu_raster::test_marching_cubes_meshes_match_reference",
-    ],
-    "(anonymous namespace)::raster_vnormal_kernel(float const*, long const*, int const*, long long, long long const*, int*, double*)": [
-        "test_gpu_raster::test_marching_cubes_meshes_match_reference",
-        "test_gpu_raster::test_hand_placed_triangles_match_reference",
-    ],
-    f"(anonymous namespace)::raster_shade_kernel(unsigned long long const*, int, long const*, long long, float const*, {_PROJ}, int const*, double const*, unsigned char*, long*, float*, float*, float*)": [
-        "test_gpu_raster::test_hand_placed_triangles_match_reference",
-        "test_gpu_raster::test_marching_cubes_meshes_match_reference",
-        "test_gpu_raster::test_empty_mesh_is_all_background",
-    ],
-}
-
-
-def _tool(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tools", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-@pytest.fixture(scope="module")
-def raster_library():
-    """build() is incremental: it builds libenarf_raster.so next to libenarf_hip.so if this checkout has not yet"""
-    from enarf_gan_amd import build
-    build.build()
-    return build.RASTER_LIB
-
+ROOT = L.ROOT
 
 # ------------------------------------------------------------------------------------------------- the reference
 def _K(fx, fy, cx, cy):
@@ -151,38 +91,12 @@ def test_reference_sphere_silhouette_is_the_analytic_disc():
 
 
 # ------------------------------------------------------------------------------------------------- the library
-def _declared():
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "enarf_raster.h")).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(enarf_raster_[a-z0-9_]+)\s*\(", src)))
-
-
-def test_header_symbols_exported_and_bound(raster_library):
+def test_header_symbols_exported_and_bound():
+    """what is specific to this library; tests/test_libraries_cpu.py holds the checks every library gets"""
     from enarf_gan_amd import _raster_lib
-    lib = C.CDLL(raster_library)
-    declared = _declared()
-    assert declared == ["enarf_raster_abi_version", "enarf_raster_last_error", "enarf_raster_mesh",
-                        "enarf_raster_workspace_bytes"]
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in enarf_raster.h but not exported by libenarf_raster.so"
-    assert set(_raster_lib.SIGNATURES) == set(declared)
-    assert _raster_lib.load().enarf_raster_abi_version() == _raster_lib.ABI_VERSION == 1
-    assert "#define ENARF_RASTER_ABI_VERSION 1" in open(os.path.join(ROOT, "include", "enarf_raster.h")).read()
-
-
-def test_raster_kernels_are_separate_and_each_has_gpu_tests(raster_library):
-    from enarf_gan_amd import build
-    chains = _tool("check_mfma_chains")
-    built = set(chains.kernel_symbols(raster_library))
-    assert built == set(RASTER_KERNEL_TESTS), sorted(built ^ set(RASTER_KERNEL_TESTS))
-    assert not built & set(chains.kernel_symbols(build.LIB)), "a raster kernel inside libenarf_hip.so"
-    assert not built & set(chains.kernel_symbols(build.MESH_LIB)), "a raster kernel inside libenarf_mesh.so"
-    tree = ast.parse(open(os.path.join(TESTS, "test_gpu_raster.py")).read())
-    functions = {n.name for n in tree.body if isinstance(n, ast.FunctionDef)}
-    for kernel, tests in RASTER_KERNEL_TESTS.items():
-        assert tests, kernel
-        for t in tests:
-            module, func = t.split("::")
-            assert module == "test_gpu_raster" and func in functions, f"{kernel}: {t} does not exist"
+    assert L.declared("raster") == ["enarf_raster_abi_version", "enarf_raster_last_error", "enarf_raster_mesh",
+                                    "enarf_raster_workspace_bytes"]
+    assert _raster_lib.ABI_VERSION == 1
 
 
 def test_sources_read_no_environment_and_hold_no_assembly():
@@ -190,8 +104,9 @@ def test_sources_read_no_environment_and_hold_no_assembly():
     assert "getenv" not in src and "asm" not in src
 
 
-def test_argument_checks_need_no_device(raster_library):
+def test_argument_checks_need_no_device():
     from enarf_gan_amd import _raster_lib
+    L.library("raster")
     lib = _raster_lib.load()
     ws = lib.enarf_raster_workspace_bytes
     assert ws(-1, 0, 512) == 0 and ws(0, -1, 512) == 0
@@ -216,7 +131,7 @@ def test_argument_checks_need_no_device(raster_library):
     assert mesh(1, 3, None, 1, 1, 32, 16, 1, 1, None, None, None, None, None) == -1     # triangles null with T > 0
 
 
-def test_host_layer_has_no_cpu_fallback(raster_library):
+def test_host_layer_has_no_cpu_fallback():
     from enarf_gan_amd._lib import EnarfHipError
     from enarf_gan_amd.libraries.NARF.mesh_rendering import rasterize_mesh
     verts = torch.zeros(3, 3)

@@ -59,47 +59,79 @@ KERNEL_TESTS = {
         "test_gpu_gan2d::test_upfirdn2d_pipeline_planes"],
     # ---- tri-plane sampler (csrc/enarf_sampler.hip)
     f"void enarf::pack_kernel<8>({_PACK})": [
-        "test_gpu_parity::test_sampler_fast_path_vs_oracle", "test_gpu_parity::test_sampler_padding_modes_vs_torch"],
+        "test_gpu_parity::test_sampler_fast_path_vs_oracle", "test_gpu_parity::test_sampler_padding_modes_vs_torch",
+        "test_gpu_sampler_referee::test_sampler_forward_on_decisions"],
     f"void enarf::pack_kernel<16>({_PACK})": [
-        "test_gpu_parity::test_sampler_fast_path_vs_oracle", "test_gpu_parity::test_sampler_fast_path_channel_widths_at_tile_edges"],
+        "test_gpu_parity::test_sampler_fast_path_vs_oracle", "test_gpu_parity::test_sampler_fast_path_channel_widths_at_tile_edges",
+        "test_gpu_sampler_referee::test_sampler_forward_on_decisions"],
     f"void enarf::pack_kernel<32>({_PACK})": [
         "test_gpu_parity::test_sampler_fast_path_vs_oracle", "test_gpu_parity::test_render_vs_oracle_and_golden",
-        "test_gpu_parity::test_query_vs_oracle_and_golden"],
+        "test_gpu_parity::test_query_vs_oracle_and_golden",
+        "test_gpu_sampler_referee::test_sampler_forward_on_decisions",
+        "test_gpu_sampler_referee::test_sampler_backward_fast_path_on_decisions"],
     f"void enarf::pack_kernel<64>({_PACK})": [
-        "test_gpu_parity::test_sampler_fast_path_vs_oracle", "test_gpu_parity::test_sampler_fast_path_channel_widths_at_tile_edges"],
+        "test_gpu_parity::test_sampler_fast_path_vs_oracle", "test_gpu_parity::test_sampler_fast_path_channel_widths_at_tile_edges",
+        "test_gpu_sampler_referee::test_sampler_forward_on_decisions"],
     f"void enarf::sample_fwd_cl<1>({_SAMPLER})": [
-        "test_gpu_parity::test_sampler_fast_path_vs_oracle", "test_gpu_parity::test_sampler_padding_modes_vs_torch"],
+        "test_gpu_parity::test_sampler_fast_path_vs_oracle", "test_gpu_parity::test_sampler_padding_modes_vs_torch",
+        "test_gpu_sampler_referee::test_sampler_forward_on_decisions"],
     f"void enarf::sample_fwd_cl<2>({_SAMPLER})": [
-        "test_gpu_parity::test_sampler_fast_path_vs_oracle", "test_gpu_parity::test_sampler_fast_path_channel_widths_at_tile_edges"],
+        "test_gpu_parity::test_sampler_fast_path_vs_oracle", "test_gpu_parity::test_sampler_fast_path_channel_widths_at_tile_edges",
+        "test_gpu_sampler_referee::test_sampler_forward_on_decisions"],
     f"void enarf::sample_fwd_cl<4>({_SAMPLER})": [
-        "test_gpu_parity::test_sampler_fast_path_vs_oracle", "test_gpu_api::test_sampler_autograd_function_gives_true_gradients"],
+        "test_gpu_parity::test_sampler_fast_path_vs_oracle", "test_gpu_api::test_sampler_autograd_function_gives_true_gradients",
+        "test_gpu_sampler_referee::test_sampler_forward_on_decisions"],
     f"void enarf::sample_fwd_cl<8>({_SAMPLER})": [
-        "test_gpu_parity::test_sampler_fast_path_vs_oracle", "test_gpu_parity::test_sampler_fast_path_channel_widths_at_tile_edges"],
+        "test_gpu_parity::test_sampler_fast_path_vs_oracle", "test_gpu_parity::test_sampler_fast_path_channel_widths_at_tile_edges",
+        "test_gpu_sampler_referee::test_sampler_forward_on_decisions"],
     "void enarf::sample_fwd_direct<false>(float const*, float const*, float*, int, int, int, long long, enarf::SamplerCfg, int const*, int)": [
         "test_gpu_parity::test_sampler_fast_path_vs_oracle", "test_gpu_parity::test_sampler_padding_modes_vs_torch",
-        "test_gpu_parity::test_sampler_golden_fwd_bwd"],
+        "test_gpu_parity::test_sampler_golden_fwd_bwd",
+        "test_gpu_sampler_referee::test_sampler_forward_on_decisions",
+        "test_gpu_sampler_referee::test_sampler_nearest_rounds_half_away_from_zero",
+        "test_gpu_sampler_referee::test_sampler_separate_planes_and_point_image"],
     "void enarf::sample_fwd_direct<true>(float const*, float const*, float*, int, int, int, long long, enarf::SamplerCfg, int const*, int)": [
-        "test_gpu_api::test_sampler_image_ids_outside_the_batch_sample_nothing", "test_gpu_api::test_sampling_api_mirror_matches_reference_golden"],
+        "test_gpu_api::test_sampler_image_ids_outside_the_batch_sample_nothing", "test_gpu_api::test_sampling_api_mirror_matches_reference_golden",
+        "test_gpu_sampler_referee::test_sampler_separate_planes_and_point_image"],
     "enarf::sample_bwd_cl32(float const*, float const*, float const*, float*, float*, int, int, long long, enarf::SamplerCfg)": [
-        "test_gpu_parity::test_sampler_backward_fast_path_vs_direct_and_autograd", "test_gpu_api::test_sampler_autograd_function_gives_true_gradients"],
+        "test_gpu_parity::test_sampler_backward_fast_path_vs_direct_and_autograd", "test_gpu_api::test_sampler_autograd_function_gives_true_gradients",
+        "test_gpu_sampler_referee::test_sampler_backward_fast_path_on_decisions",
+        "test_gpu_sampler_referee::test_sampler_backward_contention_on_one_footprint"],
     "enarf::sample_bwd_direct(float const*, float const*, float const*, float*, float*, int, int, int, long long, enarf::SamplerCfg, int, int const*, int)": [
         "test_gpu_parity::test_sampler_backward_fast_path_vs_direct_and_autograd", "test_gpu_parity::test_sampler_golden_fwd_bwd",
-        "test_gpu_api::test_sampling_api_mirror_matches_reference_golden"],
+        "test_gpu_api::test_sampling_api_mirror_matches_reference_golden",
+        "test_gpu_sampler_referee::test_sampler_backward_direct_on_decisions",
+        "test_gpu_sampler_referee::test_sampler_nearest_rounds_half_away_from_zero",
+        "test_gpu_sampler_referee::test_sampler_separate_planes_and_point_image",
+        "test_gpu_sampler_referee::test_sampler_backward_contention_on_one_footprint"],
     "enarf::unpack_add_kernel(float const*, float*, int, int, int)": [
         "test_gpu_parity::test_sampler_backward_fast_path_vs_direct_and_autograd", "test_gpu_backward::test_render_backward_matches_oracle_autograd",
         "test_gpu_backward::test_query_backward_matches_oracle_autograd",
-        "test_gpu_backward_f64::test_render_bwd_feature_gradient_channel_last"],
+        "test_gpu_backward_f64::test_render_bwd_feature_gradient_channel_last",
+        "test_gpu_sampler_referee::test_sampler_backward_fast_path_on_decisions",
+        "test_gpu_sampler_referee::test_sampler_backward_contention_on_one_footprint"],
     "enarf::warp_fwd_kernel(float const*, float const*, float*, int, int)": [
-        "test_gpu_parity::test_deformation_field_producer_vs_grid_sample", "test_gpu_backward::test_model_with_deformation_field_producer"],
+        "test_gpu_parity::test_deformation_field_producer_vs_grid_sample", "test_gpu_backward::test_model_with_deformation_field_producer",
+        "test_gpu_sampler_referee::test_warp_on_decisions_and_tails"],
     "enarf::warp_bwd_kernel(float const*, float const*, float const*, float*, float*, int, int)": [
-        "test_gpu_parity::test_deformation_field_producer_vs_grid_sample", "test_gpu_backward::test_model_with_deformation_field_producer"],
+        "test_gpu_parity::test_deformation_field_producer_vs_grid_sample", "test_gpu_backward::test_model_with_deformation_field_producer",
+        "test_gpu_sampler_referee::test_warp_on_decisions_and_tails"],
     # ---- ray sampling (csrc/enarf_raysample.hip)
     "enarf::topk_select_kernel(float const*, long long*, int, int)": [
-        "test_gpu_api::test_mask_based_sampler_matches_torch", "test_gpu_api::test_dso_generator_forward_matches_oracle_on_sampled_rays"],
+        "test_gpu_api::test_mask_based_sampler_matches_torch", "test_gpu_api::test_dso_generator_forward_matches_oracle_on_sampled_rays",
+        "test_gpu_sampler_referee::test_ray_sampler_against_the_referee",
+        "test_gpu_sampler_referee::test_ray_sampler_ties_take_the_lowest_flat_indices",
+        "test_gpu_sampler_referee::test_ray_sampler_more_ties_than_the_buffer_holds"],
     "void enarf::window_max_kernel<false>(float const*, float*, int, int, int, float const*)": [
-        "test_gpu_api::test_mask_based_sampler_matches_torch", "test_gpu_api::test_dso_generator_forward_matches_oracle_on_sampled_rays"],
+        "test_gpu_api::test_mask_based_sampler_matches_torch", "test_gpu_api::test_dso_generator_forward_matches_oracle_on_sampled_rays",
+        "test_gpu_sampler_referee::test_ray_sampler_against_the_referee",
+        "test_gpu_sampler_referee::test_ray_sampler_ties_take_the_lowest_flat_indices",
+        "test_gpu_sampler_referee::test_ray_sampler_more_ties_than_the_buffer_holds"],
     "void enarf::window_max_kernel<true>(float const*, float*, int, int, int, float const*)": [
-        "test_gpu_api::test_mask_based_sampler_matches_torch", "test_gpu_api::test_dso_generator_forward_matches_oracle_on_sampled_rays"],
+        "test_gpu_api::test_mask_based_sampler_matches_torch", "test_gpu_api::test_dso_generator_forward_matches_oracle_on_sampled_rays",
+        "test_gpu_sampler_referee::test_ray_sampler_against_the_referee",
+        "test_gpu_sampler_referee::test_ray_sampler_ties_take_the_lowest_flat_indices",
+        "test_gpu_sampler_referee::test_ray_sampler_more_ties_than_the_buffer_holds"],
     # ---- renderer forward (csrc/enarf_render.hip); mode 0 f32, 1 bf16x3, 2 bf16, 3 f16x3; second argument samples per lane
     "enarf::prepare_kernel(enarf::PrepareParams)": [
         "test_gpu_parity::test_prepare_matches_oracle", "test_gpu_parity::test_render_vs_oracle_and_golden",

@@ -1,5 +1,5 @@
 """What the ctypes bindings of the HIP libraries share (`_lib` and the `_<stem>_lib` modules, one per row of
-build.LIBRARIES): loading a library and checking its ABI, turning a return code into an exception, and the checks every
+build.ALL_LIBRARIES): loading a library and checking its ABI, turning a return code into an exception, and the checks every
 op makes on its device arguments.
 
 There is no CPU fallback anywhere: a missing library, a CPU tensor or a failed call raises EnarfHipError.

@@ -1,13 +1,14 @@
-"""Build recipe of the HIP libraries (hipcc, gfx950 only), in-tree under csrc/: LIBRARIES below is the one place a
-library is declared, one libenarf_<stem>.so per row.
+"""Build recipe of the HIP libraries (hipcc, gfx950 only), in-tree under csrc/: the tables LIBRARIES and SIDE_LIBRARIES below
+are the one place a library is declared, one libenarf_<stem>.so per row.
 
 `python -m enarf_gan_amd.build` or `build()`; `__graft_entry__.build()` calls this. The .so files are
 git-ignored but travel to the GPU box with the repo snapshot. `python -m enarf_gan_amd.build --variant NAME [-DFLAG=V ...]`
 is what tools/build_variant.sh runs: a second build of libenarf_hip.so under variants/.
 
-Adding a library: a row in LIBRARIES, its public header under include/, a binding module `_<stem>_lib.py` (constants,
-SIGNATURES, a `_loader.Library`, the ops) and a kernel -> GPU tests map in tests/kernel_coverage.py. The ABI, inventory,
-disjointness and header-tracking checks of tests/test_libraries_cpu.py run over every row.
+Adding a library: a row, its public header under include/, a binding module `_<stem>_lib.py` (constants, SIGNATURES, a
+`_loader.Library`, the ops) and a kernel -> GPU tests map. Rows of LIBRARIES have their maps in tests/kernel_coverage.py and
+are checked by tests/test_libraries_cpu.py (ABI, inventory, disjointness, header tracking); rows of SIDE_LIBRARIES have a
+registry module each (tests/<stem>_kernel_coverage.py) and get the same checks from tests/test_side_libraries_cpu.py.
 """
 from __future__ import annotations
 
@@ -30,6 +31,14 @@ LIBRARIES = {
     "photo": (["enarf_photo.hip"], "enarf_photo.h"),       # the photometric loss and image metrics of the single-scene path
     "guide": (["enarf_guide.hip"], "enarf_guide.h"),       # the mask-guidance loss of the GAN's generator
 }
+# Libraries whose kernel registry is not in tests/kernel_coverage.py (that file holds one map per row of LIBRARIES and
+# stays as it is): same recipe, same binding conventions, built and loaded with the rest; each brings its registry and the
+# checks that tests/test_libraries_cpu.py makes per row in test files of its own (libenarf_anim.so:
+# tests/anim_kernel_coverage.py, tests/test_side_libraries_cpu.py).
+SIDE_LIBRARIES = {
+    "anim": (["enarf_anim.hip"], "enarf_anim.h"),          # pose interpolation and 8-bit frames of an animation
+}
+ALL_LIBRARIES = {**LIBRARIES, **SIDE_LIBRARIES}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
          "-I", os.path.join(ROOT, "include"), "-I", CSRC]
 
@@ -48,12 +57,13 @@ def lib_deps(stem: str) -> list:
     enarf_tasks.h was added), include/enarf_hip.h, the row's own public header and this file."""
     include = os.path.join(ROOT, "include")
     return ([os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h")] +
-            [os.path.join(include, "enarf_hip.h"), os.path.join(include, LIBRARIES[stem][1]), os.path.abspath(__file__)])
+            [os.path.join(include, "enarf_hip.h"), os.path.join(include, ALL_LIBRARIES[stem][1]), os.path.abspath(__file__)])
 
 
 LIB = lib_path("hip")
 # the names earlier callers use, all read from the table
 MESH_LIB, RASTER_LIB, POSE_LIB, PHOTO_LIB, GUIDE_LIB = (lib_path(s) for s in ("mesh", "raster", "pose", "photo", "guide"))
+ANIM_LIB = lib_path("anim")
 SOURCES, HEADERS = LIBRARIES["hip"][0], lib_deps("hip")
 
 
@@ -92,9 +102,9 @@ def _make(targets, force, verbose, extra_flags) -> None:
 
 
 def build(force: bool = False, verbose: bool = False, extra_flags=()) -> str:
-    """Build every library of LIBRARIES incrementally; returns the path of libenarf_hip.so (the others are next to it,
-    at lib_path(stem))."""
-    _make([(lib_path(stem), CSRC, sources, lib_deps(stem)) for stem, (sources, _) in LIBRARIES.items()],
+    """Build every library of LIBRARIES and SIDE_LIBRARIES incrementally; returns the path of libenarf_hip.so (the others
+    are next to it, at lib_path(stem))."""
+    _make([(lib_path(stem), CSRC, sources, lib_deps(stem)) for stem, (sources, _) in ALL_LIBRARIES.items()],
           force, verbose, extra_flags)
     return LIB
 

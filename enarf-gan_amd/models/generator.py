@@ -142,6 +142,51 @@ class TriNARFGenerator(_RendererShell):
         return self.nerf.render_extracted_mesh(pose_to_camera, intrinsics, z_nerf, z_render, bone_length, voxel_size,
                                                mesh_th, truncation_psi, self.size)
 
+    def render_animation(self, key_poses, bone_length, intrinsics, z, num=100, loop=True, orbit=None, truncation_psi=0.4,
+                         frames_per_batch=8, black_bg_if_possible=False):
+        """One identity in motion, on the device from end to end: (frames (num, S, S, 3) uint8, masks (num, S, S) uint8,
+        poses (num, J, 4, 4) in key_poses' dtype), all device tensors, with no host synchronisation inside.
+
+        key_poses (K, J, 4, 4) joint-to-camera key poses on the device; z and bone_length of batch 1; intrinsics (3, 3)
+        or (1, 3, 3); num, loop and orbit as in ops.interpolate_pose (orbit: num angles on the device, a turntable). The
+        poses come from one interpolate_pose launch, the tri-plane and the background are computed once, and the frames
+        are marched frames_per_batch at a time on the shared tri-plane (render() with the tri-plane in model_input,
+        under no_grad), each chunk turned into bytes by one compose_frames launch. A chunk is one renderer batch: its
+        near / far planes are reduced over its frames and its rays are numbered batch-wide for the importance samples,
+        as in a forward() call on the chunk's frames. The bytes therefore depend on frames_per_batch (in the last bits
+        of the march): frames_per_batch=1 gives exactly the bytes of one forward() call per frame."""
+        from .. import ops
+        from ..libraries.NeRF.rendering import render
+        if not (z.shape[0] == 1 and bone_length.shape[0] == 1):
+            raise AssertionError("render_animation takes one identity: z and bone_length of batch 1")
+        per = int(frames_per_batch)
+        if per < 1:
+            raise ValueError(f"render_animation: frames_per_batch {frames_per_batch} < 1")
+        nerf, S = self.nerf, self.size
+        with torch.no_grad():
+            poses, poses32 = ops.interpolate_pose(key_poses, nerf.parent_id, num, loop, orbit, return_f32=True)
+            dev, n_frames = poses.device, poses.shape[0]
+            z_nerf, z_render, z_bg = self._latent_parts(z)
+            tri = nerf.compute_tri_plane_feature(z_nerf, bone_length, truncation_psi)
+            backdrop = self._background(z_bg, z_render, black_bg_if_possible)
+            K_inv = torch.linalg.inv_ex(torch.as_tensor(intrinsics).float().to(dev).reshape(-1, 3, 3)[:1]).inverse
+            _, pixels = self.ray_sampler(S, S, min(per, n_frames), device=dev)
+            frames = torch.empty((n_frames, S, S, 3), dtype=torch.uint8, device=dev)
+            masks = torch.empty((n_frames, S, S), dtype=torch.uint8, device=dev)
+            mlp = nerf.mlp.as_dict()
+            for a in range(0, n_frames, per):
+                b = min(a + per, n_frames)
+                c = b - a
+                bl, z_rend = bone_length.expand(c, -1, -1), z_render.expand(c, -1)
+                parts, pack = ops.prepare(poses32[a:b], bl, nerf.canonical_bone_length, z_rend, mlp, nerf.parent_id,
+                                          nerf.origin_location, nerf.coordinate_scale)
+                model_input = {"z": z_nerf, "z_rend": z_rend, "bone_length": bl, "truncation_psi": truncation_psi,
+                               "tri_plane_feature": tri}
+                color, alpha, _ = render(nerf, pixels[:c], poses32.new_empty(c, nerf.num_bone, 4, 4), K_inv.expand(c, -1, -1),
+                                         model_input=model_input, _parts=parts, _pack=pack, **self._samples)
+                ops.compose_frames(color, alpha, backdrop, out=(frames[a:b], masks[a:b]))
+        return frames, masks, poses
+
 
 class DSONARFGenerator(_RendererShell):
     def __init__(self, config, size, num_bone=1, parent_id=None, num_bone_param=None):

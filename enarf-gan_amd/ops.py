@@ -852,3 +852,37 @@ def mask_guidance_loss(fake_mask: torch.Tensor, bone_mask: torch.Tensor, backgro
         raise NotImplementedError("mask_guidance_loss: the bone mask is a target and gets no gradient; detach it")
     loss, push, bone = _MaskGuidanceLoss.apply(fake_mask, bone_mask, float(background_ratio), float(coef))
     return (loss, push, bone) if return_terms else loss
+
+
+# ------------------------------------------------------------------------------------------------- animation
+def interpolate_pose(pose_3d: torch.Tensor, parents: Sequence[int], num: int = 100, loop: bool = True,
+                     orbit: Optional[torch.Tensor] = None, return_f32: bool = False, return_bone_length: bool = False):
+    """The reference's interpolate_pose (libraries/NARF/pose_utils.py:48-115) in one launch of libenarf_anim.so: key
+    poses (K, J, 4, 4) on the device, fp64 or fp32 -> (num, J, 4, 4) in the same dtype (computed in fp64 either way;
+    the fp32 result is that rounded once). `orbit`, a (num,) device tensor of angles, turns frame i about the y axis
+    through its mean joint translation (rotate_pose_by_angle). `return_f32` adds the fp32 copy the renderer takes,
+    `return_bone_length` the (num, J - 1, 1) fp32 bone lengths of the frames. Rotations run on t = i K / num (loop) or
+    i (K - 1) / (num - 1), translations on the reference's concatenated linspace blocks of num // K or num // (K - 1)
+    frames: without loop the two clocks differ slightly, as in the reference. ValueError where the reference raises
+    (num not a multiple of the segments) or cannot run; nothing here synchronises."""
+    from . import _anim_lib
+    poses, poses32, bone = _anim_lib.interpolate_pose(pose_3d, parents, num, loop, orbit,
+                                                      want_f32=return_f32 or pose_3d.dtype == torch.float32,
+                                                      want_bone_length=return_bone_length)
+    out = (poses32 if pose_3d.dtype == torch.float32 else poses,)
+    if return_f32:
+        out += (poses32,)
+    if return_bone_length:
+        out += (bone,)
+    return out if len(out) > 1 else out[0]
+
+
+def compose_frames(color: torch.Tensor, mask: torch.Tensor, background=-1.0, return_masks: bool = True, out=None):
+    """Rendered frames to 8-bit images in one launch of libenarf_anim.so, the demo's conversion (ENARF_GAN_demo.py:70-79)
+    without the host: color (F, 3, n) or (F, 3, S, S) and mask (F, n) or (F, S, S) fp32 on the device, background a
+    number, one (1, 3, S, S) image or (F, 3, S, S) images -> frames (F, S, S, 3) uint8 = trunc(clamp((c + (1 - m) bg)
+    127.5 + 127.5, 0, 255)) and, with `return_masks`, masks (F, S, S) uint8 = trunc(clamp(255 m, 0, 255)); a NaN gives
+    0. `out` = (frames, masks or None) writes into given contiguous tensors. Nothing here synchronises."""
+    from . import _anim_lib
+    frames, masks = _anim_lib.compose_frames(color, mask, background, want_masks=return_masks, out=out)
+    return (frames, masks) if return_masks else frames

@@ -1,0 +1,86 @@
+#!/usr/bin/env python3
+"""Moving pictures of one identity of an ENARF-GAN snapshot, on the device from the key poses to the bytes:
+TriNARFGenerator.render_animation (one interpolate_pose launch, one tri-plane, the frames marched in chunks on it, one
+compose_frames launch per chunk) and a single copy of the finished uint8 frames to the host.
+
+  python tools/animate.py --snapshot snapshot_latest.pth --sample-data sample_data.pickle --canonical canonical.npy \\
+      --keys 0,7,19 --num 96 --orbit-turns 1 --out frames/        # PNGs frame_0000.png ... (PIL)
+  python tools/animate.py ... --out walk.npy                      # one (num, S, S, 3) uint8 array
+
+The key poses, the camera and the bone lengths are entries of a sample_data.pickle (formats.read_sample_data; the
+camera and bone lengths of the first key); `--canonical` is the canonical pose (24, 4, 4) the model was trained with
+(the data set's canonical.npy). The generator is built from the options below with the shipping nerf_params
+(synth.nerf_config, a tri-plane per identity) and the snapshot's weights are loaded into it; keys the snapshot lacks
+are reported. `num` must be a multiple of the number of keys (with --no-loop: of the number of keys minus one)."""
+import argparse
+import math
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from enarf_gan_amd import formats, synth  # noqa: E402
+from enarf_gan_amd.models.generator import TriNARFGenerator  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--snapshot", required=True)
+    ap.add_argument("--sample-data", required=True)
+    ap.add_argument("--canonical", required=True, help="canonical pose, .npy (24, 4, 4)")
+    ap.add_argument("--keys", default="0,1", help="comma-separated entries of the sample data used as key poses")
+    ap.add_argument("--num", type=int, default=96)
+    ap.add_argument("--no-loop", action="store_true")
+    ap.add_argument("--orbit-turns", type=float, default=0.0, help="turntable: whole turns over the sequence (0 = none)")
+    ap.add_argument("--seed", type=int, default=0, help="seed of the identity's latent")
+    ap.add_argument("--truncation-psi", type=float, default=0.4)
+    ap.add_argument("--frames-per-batch", type=int, default=8)
+    ap.add_argument("--black-background", action="store_true")
+    ap.add_argument("--size", type=int, default=128)
+    ap.add_argument("--z-dim", type=int, default=256)
+    ap.add_argument("--nc", type=int, default=48)
+    ap.add_argument("--nf", type=int, default=64)
+    ap.add_argument("--origin-location", default="center_fixed")
+    ap.add_argument("--out", required=True, help="a directory for PNGs, or a path ending in .npy")
+    args = ap.parse_args()
+
+    dev = torch.device("cuda")
+    data = formats.read_sample_data(args.sample_data)
+    keys = [int(k) for k in args.keys.split(",")]
+    cfg = synth.AttrDict(z_dim=args.z_dim, background_ratio=0.7, crop_background=True, pretrained_background=False,
+                         nerf_params=synth.nerf_config(Nc=args.nc, Nf=args.nf, origin_location=args.origin_location,
+                                                       constant_triplane=False))
+    gen = TriNARFGenerator(cfg, args.size, 24, synth.SMPL_PARENTS, 23, black_background=args.black_background)
+    gen.register_canonical_pose(np.load(args.canonical))
+    report = formats.load_generator_snapshot(args.snapshot, gen)
+    print(f"snapshot: {len(report.loaded)} tensors loaded, {len(report.missing)} missing, {len(report.ignored)} ignored"
+          + (f", iteration {report.iteration}" if report.iteration is not None else ""), file=sys.stderr)
+    gen = gen.to(dev).eval()
+
+    key_poses = torch.from_numpy(data.pose_3d[keys].astype(np.float64)).to(dev)
+    bone_length = torch.from_numpy(data.bone_length[keys[:1]].astype(np.float32)).to(dev)
+    intrinsics = torch.from_numpy(data.intrinsics[keys[0]].astype(np.float32)).to(dev)
+    shares = 3 if args.black_background else 4
+    z = torch.randn(1, args.z_dim * shares, generator=torch.Generator().manual_seed(args.seed)).to(dev)
+    orbit = None
+    if args.orbit_turns:
+        orbit = torch.arange(args.num, dtype=torch.float64, device=dev) * (2 * math.pi * args.orbit_turns / args.num)
+    frames, _, _ = gen.render_animation(key_poses, bone_length, intrinsics, z, num=args.num, loop=not args.no_loop, orbit=orbit,
+                                        truncation_psi=args.truncation_psi, frames_per_batch=args.frames_per_batch)
+    frames = frames.cpu().numpy()                                       # the one device-to-host copy
+    if args.out.endswith(".npy"):
+        np.save(args.out, frames)
+        print(args.out, frames.shape, file=sys.stderr)
+        return
+    from PIL import Image
+    os.makedirs(args.out, exist_ok=True)
+    for i, frame in enumerate(frames):
+        Image.fromarray(frame).save(os.path.join(args.out, f"frame_{i:04d}.png"))
+    print(f"{args.out}: {len(frames)} PNGs of {frames.shape[1]} x {frames.shape[2]}", file=sys.stderr)
+
+
+if __name__ == "__main__":
+    main()

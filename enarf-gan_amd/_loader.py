@@ -11,7 +11,7 @@ import os
 from typing import Optional
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-_NAMES = {"torch.float32": "fp32", "torch.float64": "fp64", "torch.int64": "int64"}
+_NAMES = {"torch.float32": "fp32", "torch.float64": "fp64", "torch.int64": "int64", "torch.int32": "int32"}
 
 
 class EnarfHipError(RuntimeError):

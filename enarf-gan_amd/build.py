@@ -33,10 +33,11 @@ LIBRARIES = {
 }
 # Libraries whose kernel registry is not in tests/kernel_coverage.py (that file holds one map per row of LIBRARIES and
 # stays as it is): same recipe, same binding conventions, built and loaded with the rest; each brings its registry and the
-# checks that tests/test_libraries_cpu.py makes per row in test files of its own (libenarf_anim.so:
-# tests/anim_kernel_coverage.py, tests/test_side_libraries_cpu.py).
+# checks that tests/test_libraries_cpu.py makes per row in test files of its own (tests/<stem>_kernel_coverage.py, e.g.
+# tests/anim_kernel_coverage.py, and tests/test_side_libraries_cpu.py, which is parametrised over this table).
 SIDE_LIBRARIES = {
     "anim": (["enarf_anim.hip"], "enarf_anim.h"),          # pose interpolation and 8-bit frames of an animation
+    "seg": (["enarf_seg.hip"], "enarf_seg.h"),             # part labels of sample points and the semantic map of a frame
 }
 ALL_LIBRARIES = {**LIBRARIES, **SIDE_LIBRARIES}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
@@ -63,7 +64,7 @@ def lib_deps(stem: str) -> list:
 LIB = lib_path("hip")
 # the names earlier callers use, all read from the table
 MESH_LIB, RASTER_LIB, POSE_LIB, PHOTO_LIB, GUIDE_LIB = (lib_path(s) for s in ("mesh", "raster", "pose", "photo", "guide"))
-ANIM_LIB = lib_path("anim")
+ANIM_LIB, SEG_LIB = lib_path("anim"), lib_path("seg")
 SOURCES, HEADERS = LIBRARIES["hip"][0], lib_deps("hip")
 
 

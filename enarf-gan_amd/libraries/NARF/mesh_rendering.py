@@ -104,17 +104,41 @@ def marching_cubes(volume: torch.Tensor, isovalue: float):
 
 
 @torch.no_grad()
+def point_part_labels(model, pose_to_camera: torch.Tensor, points: torch.Tensor, model_input: Dict = {},
+                      points_last: bool = False, return_valid_bits: bool = False):
+    """The part that owns each point (ops.part_labels: label, top, second[, valid_bits], each (B, M)). points (B, 3, M),
+    or with `points_last` (M, 3) / (B, M, 3), in camera coordinates; pose_to_camera (B, P, 4, 4) part frames with
+    UNSCALED translation, as for density_volume. One launch; the tri-plane is the one the density sweep reads."""
+    from ..NeRF.rendering import _parts_from_part_poses
+    parts = _parts_from_part_poses(model, pose_to_camera, model_input["bone_length"])
+    tri = model_input.get("tri_plane_feature")
+    if tri is None:
+        tri = model.tri_plane if model.uses_warp else model.compute_tri_plane_feature(
+            model_input.get("z"), model_input["bone_length"], model_input.get("truncation_psi", 1))
+    if tri.shape[0] > 1 and tri.stride(0) == 0:       # an expanded constant tri-plane
+        tri = tri[:1]
+    cs = model.coordinate_scale
+    flags = model.kernel_flags()
+    return ops.part_labels(points.float() * cs if cs != 1 else points.float(), parts, model.canonical_pose, tri.detach(),
+                           clamp_mask=flags["clamp_mask"], uniform_part_weight=flags["uniform_part_weight"],
+                           points_last=points_last, return_valid_bits=return_valid_bits)
+
+
+@torch.no_grad()
 def extract_mesh(model, pose_to_camera: torch.Tensor, center: torch.Tensor, voxel_size: float = 0.003, mesh_th: float = 15,
-                 model_input: Dict = {}):
+                 model_input: Dict = {}, return_part_labels: bool = False):
     """create_mesh (mesh_rendering.py:50-81) on the device: density_volume -> marching_cubes -> the reference's
     transform (vertices - cube) * voxel_size + center, in fp32. Returns (vertices (V, 3), triangles (T, 3) int64) on
-    pose_to_camera's device; no texture (the rasteriser that would use it is third-party)."""
+    pose_to_camera's device; no texture (the rasteriser that would use it is third-party). `return_part_labels` adds
+    (V,) int32: the part that owns each vertex (-1: none), one point_part_labels launch over the vertex array."""
     if pose_to_camera.device.type != "cuda":
         raise _mesh_lib.EnarfHipError("extract_mesh runs on the device (there is no CPU fallback)")
     density = density_volume(model, pose_to_camera, center, voxel_size, model_input)
     cube = int(1 / voxel_size)
     vertices, triangles = marching_cubes(density, mesh_th)
     vertices = (vertices - cube) * voxel_size + center.to(vertices.device).float()[:, :, 0]
+    if return_part_labels:
+        return vertices, triangles, point_part_labels(model, pose_to_camera, vertices, model_input, points_last=True)[0][0]
     return vertices, triangles
 
 

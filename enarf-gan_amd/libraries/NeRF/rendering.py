@@ -27,6 +27,35 @@ def _parts_from_part_poses(model, pose_to_camera: torch.Tensor, bone_length: tor
 _MLP_LEAVES = ("conv.weight", "conv.modulation.weight", "conv.modulation.bias", "bias")
 
 
+def semantic_palette(num_parts: int, device=None) -> torch.Tensor:
+    """(num_parts, 3) fp32 colours in {-1, 0, 1}^3, the table of rendering.py:300-302: entry i is
+    (i // 9, (i // 3) % 3, i % 3) - 1, then every even i takes the original entry E - i, E the largest even index below
+    num_parts (seg_color[::2] = seg_color.flip(0)[1 - num_parts % 2::2]), which sets neighbouring parts apart."""
+    i = torch.arange(num_parts)
+    base = torch.stack([i // 9, (i // 3) % 3, i % 3], dim=1) - 1
+    out = base.clone()
+    even = i[::2]
+    out[even] = base[(num_parts - 1) // 2 * 2 - even]
+    return out.to(device=device, dtype=torch.float32)
+
+
+def _render_semantic(model, image_coord, inv_intrinsics, parts, tri, feat_cl, pack, Nc, Nf, render_scale, bins, seed, flags):
+    """render(semantic_map=True) without gradients: the march with its taps, the owner of every fine sample, and the
+    labels composed with the march's weights (rendering.py:298-305, :316-335 with the palette in place of the colour)."""
+    out = ops.render_fwd(image_coord, inv_intrinsics, parts, model.canonical_pose, tri, feat_cl, pack, Nc, Nf,
+                         render_scale=render_scale, bins=bins, seed=seed, mlp_mode=model.mlp_mode, debug=True, **flags)
+    t = out.taps
+    seg = {k: v for k, v in flags.items() if k in ("clamp_mask", "uniform_part_weight")}
+    labels, _, _ = ops.part_labels_on_rays(image_coord.float(), inv_intrinsics.float(), t["depth_min"], t["depth_max"],
+                                           t["bins"], parts, model.canonical_pose, tri, **seg)
+    color, part_map, part_mass = ops.semantic_composite(labels, out.fine_weights,
+                                                        semantic_palette(parts.shape[1], labels.device))
+    model.buffers_tensors.update(bins=t["bins"], fine_weights=out.fine_weights, fine_depth=out.fine_depth,
+                                 depth_min=t["depth_min"], depth_max=t["depth_max"], part_labels=labels,
+                                 part_map=part_map, part_mass=part_mass)
+    return color, out.mask, out.disparity
+
+
 class _RenderFunction(torch.autograd.Function):
     """Differentiable wrapper of the fused march: forward = enarf_prepare (MLP pack) + enarf_triplane_pack +
     enarf_render_fwd, backward = enarf_render_bwd + enarf_weight_grad (dW') + enarf_prepare_bwd + un-pack.
@@ -109,9 +138,13 @@ def render(model, image_coord: torch.Tensor, pose_to_camera: torch.Tensor, inv_i
     """image_coord (B, 1, 3, n); pose_to_camera (B, P, 4, 4) part frames -> color (B,3,n), mask (B,n), disparity (B,n).
 
     Extra keyword arguments (not in the reference): `bins` (B, n, Nf) replays given importance samples;
-    `seed` seeds the in-kernel Philox draw (default: a fresh 63-bit number from torch's CPU generator)."""
-    if semantic_map:
-        raise AssertionError("semantic map rendering will be implemented later")   # rendering.py:298
+    `seed` seeds the in-kernel Philox draw (default: a fresh 63-bit number from torch's CPU generator).
+
+    semantic_map=True (the branch the reference leaves behind `assert False`, rendering.py:298-305) returns the part
+    segmentation in place of the colour: every fine sample takes the palette colour of the part that owns it
+    (semantic_palette, ops.part_labels_on_rays) and is composed with the march's weights; mask and disparity are those of
+    the plain call. `part_map` (B, n) int32, `part_mass` (B, n) and `part_labels` (B, n, Nf) int32 are left in
+    model.buffers_tensors. Labels carry no gradient: with gradients required it raises NotImplementedError."""
     if pose_to_camera.requires_grad:
         raise NotImplementedError("Currently pose should not be differentiable")   # rendering.py:216-217
     assert pose_to_camera.shape[1] == model.num_bone
@@ -135,6 +168,9 @@ def render(model, image_coord: torch.Tensor, pose_to_camera: torch.Tensor, inv_i
             tri_graph = model._tri_plane_graph(model_input)    # tri-plane as the autograd graph sees it
         needs_grad = (needs_grad or tri_graph.requires_grad or z_rend.requires_grad or
                       any(p.requires_grad for p in params.values()))
+    if needs_grad and semantic_map:
+        raise NotImplementedError("semantic_map=True is not differentiable (part labels carry no gradient); call it "
+                                  "under torch.no_grad()")
     if needs_grad and return_intermediate:
         raise NotImplementedError("return_intermediate=True is served from the kernel's taps and is not differentiable; "
                                   "call it under torch.no_grad()")
@@ -154,6 +190,11 @@ def render(model, image_coord: torch.Tensor, pose_to_camera: torch.Tensor, inv_i
     tri, feat_cl = model._tri_plane_pair(model_input)
     if _pack is None:
         _pack = model._mlp_pack(z_rend)
+    if semantic_map:
+        if return_intermediate:
+            raise NotImplementedError("semantic_map=True with return_intermediate=True")
+        return _render_semantic(model, image_coord, inv_intrinsics, _parts, tri, feat_cl, _pack, Nc, Nf, render_scale, bins,
+                                seed, flags)
     out = ops.render_fwd(image_coord, inv_intrinsics, _parts, model.canonical_pose, tri, feat_cl, _pack, Nc, Nf,
                          render_scale=render_scale, bins=bins, seed=seed, mlp_mode=model.mlp_mode,
                          return_bins=True, debug=return_intermediate, **flags)
@@ -206,6 +247,6 @@ def render_entire_img(model, pose_to_camera: torch.Tensor, inv_intrinsics: torch
         mi["tri_plane_feature"] = mi["tri_plane_feature"][:1]
     with torch.set_grad_enabled(not no_grad):
         color, mask, disparity = render(model, img_coord, pose_to_camera[:1], inv_intrinsics, Nc=Nc, Nf=Nf,
-                                        camera_pose=camera_pose, model_input=mi)
+                                        semantic_map=semantic_map, camera_pose=camera_pose, model_input=mi)
     return (color.reshape(3, render_height, render_width), mask.reshape(render_height, render_width),
             disparity.reshape(render_height, render_width))

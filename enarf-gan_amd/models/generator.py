@@ -129,10 +129,27 @@ class TriNARFGenerator(_RendererShell):
         z_nerf, z_render, _ = self._latent_parts(z)
         return self.nerf.density_volume(pose_to_camera, z_nerf, z_render, bone_length, voxel_size, truncation_psi)
 
-    def extract_mesh(self, pose_to_camera, z, bone_length, voxel_size=0.003, mesh_th=15, truncation_psi=0.4):
-        """create_mesh's (vertices, triangles) built on the device (HIP marching cubes); one sample, as create_mesh."""
+    def extract_mesh(self, pose_to_camera, z, bone_length, voxel_size=0.003, mesh_th=15, truncation_psi=0.4,
+                     return_part_labels=False):
+        """create_mesh's (vertices, triangles) built on the device (HIP marching cubes); one sample, as create_mesh.
+        `return_part_labels` adds the (V,) int32 part that owns each vertex."""
         z_nerf, z_render, _ = self._latent_parts(z)
-        return self.nerf.extract_mesh(pose_to_camera, z_nerf, z_render, bone_length, voxel_size, mesh_th, truncation_psi)
+        return self.nerf.extract_mesh(pose_to_camera, z_nerf, z_render, bone_length, voxel_size, mesh_th, truncation_psi,
+                                      return_part_labels)
+
+    @torch.no_grad()
+    def render_part_map(self, pose_to_camera, bone_length, z, inv_intrinsics, truncation_psi=1):
+        """The part segmentation of the frames forward() renders: (semantic image (B, 3, S, S) in the colours of
+        rendering.semantic_palette, part_map (B, S, S) int32 - the part that carries the most weight along each ray, -1
+        where none does -, mask (B, S, S)), all on the device, with no host synchronisation inside."""
+        B, S = pose_to_camera.shape[0], self.size
+        _, pixels = self.ray_sampler(S, S, B, device=pose_to_camera.device)
+        z_nerf, z_render, _ = self._latent_parts(z)
+        K_inv = torch.as_tensor(inv_intrinsics).float().to(pixels.device)
+        color, mask = self.nerf(B, pixels, pose_to_camera, K_inv, z_nerf, z_render, bone_length,
+                                truncation_psi=truncation_psi, semantic_map=True, **self._samples)
+        part_map = self.nerf.buffers_tensors["part_map"]
+        return color.reshape(B, 3, S, S), part_map.reshape(B, S, S), mask.reshape(B, S, S)
 
     def render_extracted_mesh(self, pose_to_camera, intrinsics, z, bone_length, voxel_size=0.003, mesh_th=15,
                               truncation_psi=0.4):

@@ -296,8 +296,10 @@ class TriPlaneNARF(nn.Module):
     # ---- the reference's entry points -------------------------------------------------------------------------------
     def forward(self, batchsize, sampled_img_coord, pose_to_camera, inv_intrinsics, z, z_rend, bone_length,
                 render_scale=1, Nc=64, Nf=128, return_intermediate=False, truncation_psi=1,
-                camera_pose: Optional[torch.Tensor] = None, return_disparity=False, bins=None, seed=None):
-        """NARFBase.forward (libraries/NARF/base.py:26-51): raw 24-joint poses in, colour/mask(/disparity) out.
+                camera_pose: Optional[torch.Tensor] = None, return_disparity=False, bins=None, seed=None,
+                semantic_map=False):
+        """NARFBase.forward (libraries/NARF/base.py:26-51): raw 24-joint poses in, colour/mask(/disparity) out;
+        `semantic_map` (not in the reference's forward) is render()'s flag: the part segmentation in place of the colour.
 
         One enarf_prepare launch (part frames + modulated MLP weights) then one enarf_render_fwd launch."""
         model_input = {"z": z, "z_rend": z_rend, "bone_length": bone_length, "truncation_psi": truncation_psi}
@@ -306,7 +308,7 @@ class TriPlaneNARF(nn.Module):
         # part-frame count only (the kernel reads `parts`); keeps render()'s shape assertion meaningful
         pose_parts = pose_to_camera.new_empty(pose_to_camera.shape[0], self.num_bone, 4, 4)
         res = render(self, sampled_img_coord, pose_parts, inv_intrinsics, render_scale, Nc, Nf,
-                     return_intermediate=return_intermediate, camera_pose=camera_pose,
+                     semantic_map=semantic_map, return_intermediate=return_intermediate, camera_pose=camera_pose,
                      model_input=model_input, _parts=parts, _pack=pack, bins=bins, seed=seed)
         if return_intermediate:                       # libraries/NeRF/base.py:112-114
             return res[0], res[1], res[3]
@@ -332,12 +334,26 @@ class TriPlaneNARF(nn.Module):
         center, pose_parts, model_input = self._mesh_inputs(pose_to_camera, z, z_rend, bone_length, truncation_psi)
         return density_volume(self, pose_parts, center, voxel_size, model_input)
 
-    def extract_mesh(self, pose_to_camera, z, z_rend, bone_length, voxel_size=0.003, mesh_th=15, truncation_psi=0.4):
+    def extract_mesh(self, pose_to_camera, z, z_rend, bone_length, voxel_size=0.003, mesh_th=15, truncation_psi=0.4,
+                     return_part_labels=False):
         """The mesh of render_mesh / create_mesh built on the device: density sweep -> HIP marching cubes -> the
-        reference's transform (mesh_rendering.extract_mesh). Returns (vertices (V, 3), triangles (T, 3) int64)."""
+        reference's transform (mesh_rendering.extract_mesh). Returns (vertices (V, 3), triangles (T, 3) int64) and, with
+        `return_part_labels`, (V,) int32 labels: the part that owns each vertex."""
         from ..libraries.NARF.mesh_rendering import extract_mesh
         center, pose_parts, model_input = self._mesh_inputs(pose_to_camera, z, z_rend, bone_length, truncation_psi)
-        return extract_mesh(self, pose_parts, center, voxel_size, mesh_th, model_input)
+        return extract_mesh(self, pose_parts, center, voxel_size, mesh_th, model_input, return_part_labels)
+
+    def part_labels(self, points, pose_to_camera, z, bone_length, truncation_psi=1, points_last=False,
+                    return_valid_bits=False):
+        """The part that owns each point: (label (B, M) int32, top (B, M), second (B, M)[, valid_bits]) of
+        ops.part_labels. points (B, 3, M), or with `points_last` (M, 3) / (B, M, 3), in camera coordinates;
+        pose_to_camera (B, J, 4, 4) joint poses. One launch of libenarf_seg.so, no feature gather, no MLP."""
+        from ..libraries.NARF.mesh_rendering import point_part_labels
+        model_input = {"z": z, "truncation_psi": truncation_psi}
+        pose_parts, model_input["bone_length"] = self.transform_pose(pose_to_camera, bone_length)
+        if not self.uses_warp:
+            model_input["tri_plane_feature"] = self.compute_tri_plane_feature(z, bone_length, truncation_psi)
+        return point_part_labels(self, pose_parts, points, model_input, points_last, return_valid_bits)
 
     def render_extracted_mesh(self, pose_to_camera, intrinsics, z, z_rend, bone_length, voxel_size=0.003, mesh_th=15,
                               truncation_psi=0.4, img_size=128):

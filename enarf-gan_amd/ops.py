@@ -886,3 +886,40 @@ def compose_frames(color: torch.Tensor, mask: torch.Tensor, background=-1.0, ret
     from . import _anim_lib
     frames, masks = _anim_lib.compose_frames(color, mask, background, want_masks=return_masks, out=out)
     return (frames, masks) if return_masks else frames
+
+
+# ------------------------------------------------------------------------------------------------- part segmentation
+def part_labels(points: torch.Tensor, parts: torch.Tensor, canonical_pose: torch.Tensor, tri_nchw: torch.Tensor, *,
+                clamp_mask: bool = False, uniform_part_weight: bool = False, points_last: bool = False,
+                return_valid_bits: bool = False):
+    """The part that owns each point, in one launch of libenarf_seg.so: (label (B, M) int32, top (B, M), second (B, M)
+    [, valid_bits (B, M) int32]). A point is owned by the part of the largest tri-plane part probability among the parts
+    whose cube contains it (the lowest index among equals); label is -1 and top 0 where no cube does; second is the
+    runner-up's weight, -1 without one; valid_bits are the bits query_fwd(need_valid=True) returns. points (B, 3, M) in
+    the scaled camera space, or with `points_last` (M, 3) (B = 1) / (B, M, 3), read in place through their strides;
+    parts (B, P, 16) from prepare, tri_nchw the (1 or B, 96 + 3P, H, W) tri-plane. No feature gather and no MLP run,
+    nothing synchronises; M = 0 returns empty tensors without a launch."""
+    from . import _seg_lib
+    return _seg_lib.part_labels(points, parts, canonical_pose, tri_nchw, clamp_mask, uniform_part_weight, points_last,
+                                return_valid_bits)
+
+
+def part_labels_on_rays(image_coord: torch.Tensor, inv_intrinsics: torch.Tensor, depth_min: torch.Tensor,
+                        depth_max: torch.Tensor, bins: torch.Tensor, parts: torch.Tensor, canonical_pose: torch.Tensor,
+                        tri_nchw: torch.Tensor, *, clamp_mask: bool = False, uniform_part_weight: bool = False,
+                        return_valid_bits: bool = False):
+    """part_labels on the fine samples of a march, as (B, n, Nf) tensors: the points are formed in the kernel from the
+    march's taps (render_fwd(debug=True).taps: depth_min, depth_max (B, n), bins (B, n, Nf)) with the march's own
+    arithmetic, so the validity bits are the march's."""
+    from . import _seg_lib
+    return _seg_lib.part_labels_on_rays(image_coord, inv_intrinsics, depth_min, depth_max, bins, parts, canonical_pose,
+                                        tri_nchw, clamp_mask, uniform_part_weight, return_valid_bits)
+
+
+def semantic_composite(labels: torch.Tensor, fine_weights: torch.Tensor, palette: torch.Tensor):
+    """Labels along each ray to the semantic map, in one launch of libenarf_seg.so: labels (B, n, Nf) int32, fine_weights
+    (B, 1, n, Nf - 1) as the march returns them, palette (P, 3) -> (color (B, 3, n) = sum of w_i palette[label_i] over the
+    labelled samples, part_map (B, n) int32 = the part of the largest summed weight along the ray (the lowest index among
+    equals, -1 when no labelled sample has weight), part_mass (B, n) = that sum). Bit-identical from run to run."""
+    from . import _seg_lib
+    return _seg_lib.semantic_composite(labels, fine_weights, palette)

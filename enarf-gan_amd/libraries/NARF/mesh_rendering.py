@@ -7,7 +7,9 @@ is generated inside `enarf_query_fwd` (lattice mode, density only, one launch; o
 `pytorch3d`) and raises ImportError where the reference would. `extract_mesh` is the same mesh built on the device:
 `density_volume` -> `marching_cubes` (libenarf_mesh.so) -> the reference's transform; `export_obj` writes it out.
 `rasterize_mesh` is `render_mesh_`'s hard-Phong image of such a mesh, rendered on the device (libenarf_raster.so);
-`render_mesh_` itself keeps pytorch3d.
+`render_mesh_` itself keeps pytorch3d. `vertex_colors` is the radiance field's colour at the vertices, `paint_mesh` the
+image of the mesh in those colours or in the colours of its part labels (rasterize_mesh, then the deferred shading of
+libenarf_paint.so); `export_obj` and `export_ply` carry the colours and labels out.
 """
 from __future__ import annotations
 
@@ -125,33 +127,108 @@ def point_part_labels(model, pose_to_camera: torch.Tensor, points: torch.Tensor,
 
 
 @torch.no_grad()
+def vertex_colors(model, pose_to_camera: torch.Tensor, vertices: torch.Tensor, model_input: Dict = {}) -> torch.Tensor:
+    """(V, 3) fp32 in [0, 1]: (the radiance field's colour + 1) / 2 at vertices (V, 3) in camera coordinates. The field is
+    view-independent on the shipped path (no_ray_direction), so a surface point has one colour. One ops.query_fwd launch
+    over the vertex array; pose_to_camera (1, P, 4, 4) part frames with UNSCALED translation, as for point_part_labels."""
+    from ..NeRF.rendering import _parts_from_part_poses
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError(f"vertex_colors takes (V, 3) vertices, got {tuple(vertices.shape)}")
+    parts = _parts_from_part_poses(model, pose_to_camera, model_input["bone_length"])
+    tri, feat_cl = model._tri_plane_pair(model_input)
+    pack = model._mlp_pack(model_input["z_rend"])
+    cs = model.coordinate_scale
+    points = (vertices.float() * cs if cs != 1 else vertices.float()).t()[None].contiguous()
+    _, color = ops.query_fwd(points, parts, model.canonical_pose, tri, feat_cl, pack, mlp_mode=model.mlp_mode,
+                             need_color=True, **model.kernel_flags())
+    return ((color[0] + 1) / 2).t().contiguous()
+
+
+@torch.no_grad()
 def extract_mesh(model, pose_to_camera: torch.Tensor, center: torch.Tensor, voxel_size: float = 0.003, mesh_th: float = 15,
-                 model_input: Dict = {}, return_part_labels: bool = False):
+                 model_input: Dict = {}, return_part_labels: bool = False, return_colors: bool = False):
     """create_mesh (mesh_rendering.py:50-81) on the device: density_volume -> marching_cubes -> the reference's
     transform (vertices - cube) * voxel_size + center, in fp32. Returns (vertices (V, 3), triangles (T, 3) int64) on
-    pose_to_camera's device; no texture (the rasteriser that would use it is third-party). `return_part_labels` adds
-    (V,) int32: the part that owns each vertex (-1: none), one point_part_labels launch over the vertex array."""
+    pose_to_camera's device. `return_part_labels` adds (V,) int32: the part that owns each vertex (-1: none), one
+    point_part_labels launch over the vertex array; `return_colors` adds (V, 3) fp32 in [0, 1], the field's colour at
+    each vertex (vertex_colors, one query launch); with both the result is (vertices, triangles, labels, colors)."""
     if pose_to_camera.device.type != "cuda":
         raise _mesh_lib.EnarfHipError("extract_mesh runs on the device (there is no CPU fallback)")
     density = density_volume(model, pose_to_camera, center, voxel_size, model_input)
     cube = int(1 / voxel_size)
     vertices, triangles = marching_cubes(density, mesh_th)
     vertices = (vertices - cube) * voxel_size + center.to(vertices.device).float()[:, :, 0]
+    out = (vertices, triangles)
     if return_part_labels:
-        return vertices, triangles, point_part_labels(model, pose_to_camera, vertices, model_input, points_last=True)[0][0]
-    return vertices, triangles
+        out += (point_part_labels(model, pose_to_camera, vertices, model_input, points_last=True)[0][0],)
+    if return_colors:
+        out += (vertex_colors(model, pose_to_camera, vertices, model_input),)
+    return out
 
 
-def export_obj(vertices, triangles, path: str) -> None:
-    """Plain-text Wavefront OBJ ("v x y z" lines, then "f a b c" with 1-based indices), as mcubes.export_obj writes."""
+def _host(a, dtype=None):
     import numpy as np
-    v = vertices.detach().cpu().numpy() if isinstance(vertices, torch.Tensor) else np.asarray(vertices)
-    f = triangles.detach().cpu().numpy() if isinstance(triangles, torch.Tensor) else np.asarray(triangles)
+    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    return a if dtype is None else a.astype(dtype)
+
+
+def export_obj(vertices, triangles, path: str, colors=None) -> None:
+    """Plain-text Wavefront OBJ ("v x y z" lines, then "f a b c" with 1-based indices), as mcubes.export_obj writes.
+    With `colors` (V, 3) in [0, 1] the vertex lines are "v x y z r g b", the extension MeshLab and Blender read."""
+    import numpy as np
+    v, f = _host(vertices), _host(triangles)
+    c = None if colors is None else _host(colors)
+    if c is not None and c.shape != (len(v), 3):
+        raise ValueError(f"export_obj takes ({len(v)}, 3) colors, got {c.shape}")
     with open(path, "w") as fh:
-        for x in v:
-            fh.write("v %r %r %r\n" % (float(x[0]), float(x[1]), float(x[2])))
+        for i, x in enumerate(v):
+            if c is None:
+                fh.write("v %r %r %r\n" % (float(x[0]), float(x[1]), float(x[2])))
+            else:
+                fh.write("v %r %r %r %r %r %r\n" % (float(x[0]), float(x[1]), float(x[2]),
+                                                   float(c[i, 0]), float(c[i, 1]), float(c[i, 2])))
         for t in f.astype(np.int64) + 1:
             fh.write("f %d %d %d\n" % (t[0], t[1], t[2]))
+
+
+def export_ply(vertices, triangles, path: str, colors=None, labels=None) -> None:
+    """Binary little-endian PLY: per vertex float x y z, with `colors` (V, 3) in [0, 1] uchar red green blue =
+    floor(255 clamp(c, 0, 1)) (the bytes the painted image uses), with `labels` (V,) int `part`; per face
+    `list uchar int vertex_indices` (0-based)."""
+    import numpy as np
+    v, f = _host(vertices, np.float32).reshape(-1, 3), _host(triangles, np.int64).reshape(-1, 3)
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}",
+              "property float x", "property float y", "property float z"]
+    if colors is not None:
+        c = _host(colors, np.float64)
+        if c.shape != (len(v), 3):
+            raise ValueError(f"export_ply takes ({len(v)}, 3) colors, got {c.shape}")
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        header += ["property uchar red", "property uchar green", "property uchar blue"]
+    if labels is not None:
+        lab = _host(labels)
+        if lab.shape != (len(v),):
+            raise ValueError(f"export_ply takes ({len(v)},) labels, got {lab.shape}")
+        fields.append(("part", "<i4"))
+        header.append("property int part")
+    if len(f) and (f.min() < -2 ** 31 or f.max() >= 2 ** 31):
+        raise ValueError("export_ply: a vertex index does not fit the int of the face list")
+    header += [f"element face {len(f)}", "property list uchar int vertex_indices", "end_header"]
+    vert = np.zeros(len(v), dtype=fields)
+    vert["x"], vert["y"], vert["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if colors is not None:
+        with np.errstate(invalid="ignore"):
+            byte = np.floor(255 * np.clip(np.nan_to_num(c, nan=0.0), 0, 1)).astype(np.uint8)
+        vert["red"], vert["green"], vert["blue"] = byte[:, 0], byte[:, 1], byte[:, 2]
+    if labels is not None:
+        vert["part"] = lab
+    face = np.zeros(len(f), dtype=[("n", "u1"), ("v", "<i4", (3,))])
+    face["n"], face["v"] = 3, f
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(header) + "\n").encode("ascii"))
+        fh.write(vert.tobytes())
+        fh.write(face.tobytes())
 
 
 def rasterize_mesh(vertices: torch.Tensor, triangles: torch.Tensor, intrinsics, img_size: int, render_size: int = 512):
@@ -166,6 +243,19 @@ def rasterize_mesh(vertices: torch.Tensor, triangles: torch.Tensor, intrinsics, 
     (ambient 0.5, diffuse 0.3, specular 0.2, shininess 64) with a white mesh and the light at the camera; background
     white. The full contract, and what is not drawn, is in include/enarf_raster.h. No CPU fallback."""
     return _raster_lib.rasterize_mesh(vertices, triangles, intrinsics, img_size, render_size)
+
+
+def paint_mesh(vertices: torch.Tensor, triangles: torch.Tensor, intrinsics, img_size: int, render_size: int = 512,
+               vertex_colors=None, vertex_labels=None, palette=None, lit: bool = True):
+    """The mesh drawn in its vertex colours (V, 3) fp32 in [0, 1], or in the palette (P, 3) colours of its vertex labels
+    (V,) int32: rasterize_mesh, then ops.shade_fragments on its fragment buffers (libenarf_paint.so, one launch more),
+    with no host synchronisation. Returns (the RasterizedMesh of rasterize_mesh, the namedtuple (image (R, R, 3) uint8,
+    albedo, shaded (R, R, 3) fp32) of shade_fragments). With `lit` the colours take the rasteriser's hard-Phong terms
+    (white colours then give rasterize_mesh's own image); without, the image is the colour itself. No CPU fallback."""
+    fragments = rasterize_mesh(vertices, triangles, intrinsics, img_size, render_size)
+    painted = ops.shade_fragments(fragments.pix_to_face, fragments.bary, fragments.normals, vertices, triangles,
+                                  vertex_colors=vertex_colors, vertex_labels=vertex_labels, palette=palette, lit=lit)
+    return fragments, painted
 
 
 def render_mesh_(meshes, intrinsics, img_size, render_size=512):

@@ -130,12 +130,13 @@ class TriNARFGenerator(_RendererShell):
         return self.nerf.density_volume(pose_to_camera, z_nerf, z_render, bone_length, voxel_size, truncation_psi)
 
     def extract_mesh(self, pose_to_camera, z, bone_length, voxel_size=0.003, mesh_th=15, truncation_psi=0.4,
-                     return_part_labels=False):
+                     return_part_labels=False, return_colors=False):
         """create_mesh's (vertices, triangles) built on the device (HIP marching cubes); one sample, as create_mesh.
-        `return_part_labels` adds the (V,) int32 part that owns each vertex."""
+        `return_part_labels` adds the (V,) int32 part that owns each vertex, `return_colors` the (V, 3) fp32 colour of
+        the field at each vertex, in [0, 1] (after the labels when both are asked for)."""
         z_nerf, z_render, _ = self._latent_parts(z)
         return self.nerf.extract_mesh(pose_to_camera, z_nerf, z_render, bone_length, voxel_size, mesh_th, truncation_psi,
-                                      return_part_labels)
+                                      return_part_labels, return_colors)
 
     @torch.no_grad()
     def render_part_map(self, pose_to_camera, bone_length, z, inv_intrinsics, truncation_psi=1):
@@ -158,6 +159,79 @@ class TriNARFGenerator(_RendererShell):
         z_nerf, z_render, _ = self._latent_parts(z)
         return self.nerf.render_extracted_mesh(pose_to_camera, intrinsics, z_nerf, z_render, bone_length, voxel_size,
                                                mesh_th, truncation_psi, self.size)
+
+    def render_colored_mesh(self, pose_to_camera, intrinsics, z, bone_length, voxel_size=0.003, mesh_th=15,
+                            truncation_psi=0.4, color="field", lit=True):
+        """render_extracted_mesh in colour: the mesh carries the radiance field's colour at each vertex (color="field")
+        or the colour of the part that owns it (color="parts", (semantic_palette + 1) / 2), drawn by the HIP rasteriser
+        and the HIP deferred shading; `lit` keeps the hard-Phong terms. (image (512, 512, 3) uint8 numpy, (vertices,
+        triangles, colours (V, 3) fp32 or labels (V,) int32)); one sample, as render_mesh."""
+        z_nerf, z_render, _ = self._latent_parts(z)
+        return self.nerf.render_colored_mesh(pose_to_camera, intrinsics, z_nerf, z_render, bone_length, voxel_size,
+                                             mesh_th, truncation_psi, self.size, color, lit)
+
+    def render_mesh_turntable(self, pose_to_camera, intrinsics, z, bone_length, angles, voxel_size=0.003, mesh_th=15,
+                              truncation_psi=0.4, color="field", lit=True, render_size=512):
+        """The coloured mesh of render_colored_mesh on a turntable: (num, R, R, 3) uint8 frames on the device, frame i
+        the mesh turned by angles[i] about the y axis through the mean joint translation (rotate_mesh_by_angle). The
+        mesh and its colours or labels are extracted once; every angle is one rotate_mesh_by_angle, one rasterize_mesh
+        and one shade_fragments, with no host synchronisation inside. angles: num numbers or a (num,) tensor."""
+        from .. import ops
+        from ..libraries.NARF.mesh_rendering import rasterize_mesh
+        from ..libraries.NARF.pose_utils import rotate_mesh_by_angle
+        z_nerf, z_render, _ = self._latent_parts(z)
+        vertices, triangles, _, how = self.nerf._colored_mesh(pose_to_camera, z_nerf, z_render, bone_length, voxel_size,
+                                                              mesh_th, truncation_psi, color)
+        dev, R = vertices.device, int(render_size)
+        angles = torch.as_tensor(angles).to(device=dev, dtype=torch.float32).reshape(-1)
+        frames = torch.empty((angles.shape[0], R, R, 3), dtype=torch.uint8, device=dev)
+        pose = pose_to_camera.to(device=dev, dtype=torch.float32)
+        for i in range(angles.shape[0]):
+            turned = rotate_mesh_by_angle(pose, (vertices,), angles[i:i + 1])[0].contiguous()
+            f = rasterize_mesh(turned, triangles, intrinsics, self.size, R)
+            frames[i] = ops.shade_fragments(f.pix_to_face, f.bary, f.normals, turned, triangles, lit=lit, **how).image
+        return frames
+
+    def render_part_animation(self, key_poses, bone_length, intrinsics, z, num=100, loop=True, orbit=None,
+                              truncation_psi=0.4, frames_per_batch=8, background=1.0):
+        """render_animation of the part segmentation: (frames (num, S, S, 3) uint8 in the colours of semantic_palette over
+        `background` (a number in [-1, 1], white by default), part_maps (num, S, S) int32 - the part that carries the most
+        weight along each ray, -1 where none does -, poses (num, J, 4, 4) in key_poses' dtype), all device tensors, with
+        no host synchronisation inside. The structure is render_animation's: one interpolate_pose launch, one tri-plane,
+        the frames marched frames_per_batch at a time through render(..., semantic_map=True), each chunk turned into
+        bytes by one compose_frames launch; frames_per_batch=1 gives the bytes of one render() call per frame."""
+        from .. import ops
+        from ..libraries.NeRF.rendering import render
+        if not (z.shape[0] == 1 and bone_length.shape[0] == 1):
+            raise AssertionError("render_part_animation takes one identity: z and bone_length of batch 1")
+        per = int(frames_per_batch)
+        if per < 1:
+            raise ValueError(f"render_part_animation: frames_per_batch {frames_per_batch} < 1")
+        nerf, S = self.nerf, self.size
+        with torch.no_grad():
+            poses, poses32 = ops.interpolate_pose(key_poses, nerf.parent_id, num, loop, orbit, return_f32=True)
+            dev, n_frames = poses.device, poses.shape[0]
+            z_nerf, z_render, _ = self._latent_parts(z)
+            tri = nerf.compute_tri_plane_feature(z_nerf, bone_length, truncation_psi)
+            K_inv = torch.linalg.inv_ex(torch.as_tensor(intrinsics).float().to(dev).reshape(-1, 3, 3)[:1]).inverse
+            _, pixels = self.ray_sampler(S, S, min(per, n_frames), device=dev)
+            frames = torch.empty((n_frames, S, S, 3), dtype=torch.uint8, device=dev)
+            part_maps = torch.empty((n_frames, S, S), dtype=torch.int32, device=dev)
+            mlp = nerf.mlp.as_dict()
+            for a in range(0, n_frames, per):
+                b = min(a + per, n_frames)
+                c = b - a
+                bl, z_rend = bone_length.expand(c, -1, -1), z_render.expand(c, -1)
+                parts, pack = ops.prepare(poses32[a:b], bl, nerf.canonical_bone_length, z_rend, mlp, nerf.parent_id,
+                                          nerf.origin_location, nerf.coordinate_scale)
+                model_input = {"z": z_nerf, "z_rend": z_rend, "bone_length": bl, "truncation_psi": truncation_psi,
+                               "tri_plane_feature": tri}
+                color, alpha, _ = render(nerf, pixels[:c], poses32.new_empty(c, nerf.num_bone, 4, 4), K_inv.expand(c, -1, -1),
+                                         semantic_map=True, model_input=model_input, _parts=parts, _pack=pack,
+                                         **self._samples)
+                ops.compose_frames(color, alpha, background, return_masks=False, out=(frames[a:b], None))
+                part_maps[a:b] = nerf.buffers_tensors["part_map"].reshape(c, S, S)
+        return frames, part_maps, poses
 
     def render_animation(self, key_poses, bone_length, intrinsics, z, num=100, loop=True, orbit=None, truncation_psi=0.4,
                          frames_per_batch=8, black_bg_if_possible=False):

@@ -335,13 +335,14 @@ class TriPlaneNARF(nn.Module):
         return density_volume(self, pose_parts, center, voxel_size, model_input)
 
     def extract_mesh(self, pose_to_camera, z, z_rend, bone_length, voxel_size=0.003, mesh_th=15, truncation_psi=0.4,
-                     return_part_labels=False):
+                     return_part_labels=False, return_colors=False):
         """The mesh of render_mesh / create_mesh built on the device: density sweep -> HIP marching cubes -> the
         reference's transform (mesh_rendering.extract_mesh). Returns (vertices (V, 3), triangles (T, 3) int64) and, with
-        `return_part_labels`, (V,) int32 labels: the part that owns each vertex."""
+        `return_part_labels`, (V,) int32 labels: the part that owns each vertex; with `return_colors`, (V, 3) fp32 in
+        [0, 1]: the field's colour at each vertex (after the labels when both are asked for)."""
         from ..libraries.NARF.mesh_rendering import extract_mesh
         center, pose_parts, model_input = self._mesh_inputs(pose_to_camera, z, z_rend, bone_length, truncation_psi)
-        return extract_mesh(self, pose_parts, center, voxel_size, mesh_th, model_input, return_part_labels)
+        return extract_mesh(self, pose_parts, center, voxel_size, mesh_th, model_input, return_part_labels, return_colors)
 
     def part_labels(self, points, pose_to_camera, z, bone_length, truncation_psi=1, points_last=False,
                     return_valid_bits=False):
@@ -365,6 +366,32 @@ class TriPlaneNARF(nn.Module):
                                                 truncation_psi)
         image = rasterize_mesh(vertices, triangles, intrinsics, img_size).image
         return image.cpu().numpy(), (vertices, triangles)
+
+    def _colored_mesh(self, pose_to_camera, z, z_rend, bone_length, voxel_size, mesh_th, truncation_psi, color):
+        """(vertices, triangles, colours or labels, the keywords paint_mesh takes for them) of render_colored_mesh"""
+        from ..libraries.NeRF.rendering import semantic_palette
+        if color not in ("field", "parts"):
+            raise ValueError(f"color is 'field' (the radiance field's colour) or 'parts' (the part labels), got {color!r}")
+        vertices, triangles, paint = self.extract_mesh(pose_to_camera, z, z_rend, bone_length, voxel_size, mesh_th,
+                                                       truncation_psi, return_part_labels=color == "parts",
+                                                       return_colors=color == "field")
+        if color == "field":
+            return vertices, triangles, paint, dict(vertex_colors=paint)
+        palette = (semantic_palette(self.num_bone, vertices.device) + 1) / 2
+        return vertices, triangles, paint, dict(vertex_labels=paint, palette=palette)
+
+    def render_colored_mesh(self, pose_to_camera, intrinsics, z, z_rend, bone_length, voxel_size=0.003, mesh_th=15,
+                            truncation_psi=0.4, img_size=128, color="field", lit=True):
+        """render_extracted_mesh in colour: extract_mesh with the field's colour at each vertex (color="field") or the
+        part that owns it (color="parts", drawn in (semantic_palette + 1) / 2, a vertex no part owns in grey) ->
+        paint_mesh (HIP rasteriser, HIP deferred shading, 512 x 512), one host copy of the finished image. `lit` keeps
+        the hard-Phong terms of render_extracted_mesh; without it the image is the colour itself. Returns (image
+        (512, 512, 3) uint8 numpy, (vertices, triangles, colours (V, 3) fp32 or labels (V,) int32)); one sample."""
+        from ..libraries.NARF.mesh_rendering import paint_mesh
+        vertices, triangles, paint, how = self._colored_mesh(pose_to_camera, z, z_rend, bone_length, voxel_size, mesh_th,
+                                                             truncation_psi, color)
+        _, painted = paint_mesh(vertices, triangles, intrinsics, img_size, lit=lit, **how)
+        return painted.image.cpu().numpy(), (vertices, triangles, paint)
 
     def _mesh_inputs(self, pose_to_camera, z, z_rend, bone_length, truncation_psi):
         if not ((z is None or z.shape[0] == 1) and (bone_length is None or bone_length.shape[0] == 1)):

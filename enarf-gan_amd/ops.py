@@ -923,3 +923,22 @@ def semantic_composite(labels: torch.Tensor, fine_weights: torch.Tensor, palette
     equals, -1 when no labelled sample has weight), part_mass (B, n) = that sum). Bit-identical from run to run."""
     from . import _seg_lib
     return _seg_lib.semantic_composite(labels, fine_weights, palette)
+
+
+# ------------------------------------------------------------------------------------------------- coloured meshes
+def shade_fragments(pix_to_face: torch.Tensor, bary: torch.Tensor, normals: torch.Tensor, vertices: torch.Tensor,
+                    triangles: torch.Tensor, *, vertex_colors: Optional[torch.Tensor] = None,
+                    vertex_labels: Optional[torch.Tensor] = None, palette: Optional[torch.Tensor] = None, lit: bool = True,
+                    background=1.0, neutral=0.5):
+    """The fragment buffers of rasterize_mesh to a coloured image, in one launch of libenarf_paint.so: the namedtuple
+    (image (R, R, 3) uint8, albedo (R, R, 3) fp32, shaded (R, R, 3) fp32). pix_to_face (R, R) int64, bary and normals
+    (R, R, 3) fp32 as rasterize_mesh returns them, vertices (V, 3) fp32, triangles (T, 3) int64 and exactly one of
+    vertex_colors (V, 3) fp32 in [0, 1] or vertex_labels (V,) int32 with palette (P, 3) fp32 in [0, 1]. The texel (albedo)
+    is the barycentric mix of the three vertex colours, or the palette colour of the corner with the largest barycentric
+    (`neutral` for a label outside [0, P)); `lit` applies the rasteriser's hard-Phong terms to it, shaded = texel
+    (0.5 + 0.3 max(c, 0)) + 0.2 specular, else shaded = texel; a pixel without a face takes `background`; image =
+    floor(255 clamp(shaded, 0, 1)). background and neutral are a number or three. Computed in fp64 from the fp32 inputs;
+    bit-identical from run to run, nothing synchronises. ValueError for shapes or dtypes it does not take."""
+    from . import _paint_lib
+    return _paint_lib.shade_fragments(pix_to_face, bary, normals, vertices, triangles, vertex_colors, vertex_labels, palette,
+                                      lit, background, neutral)

@@ -6,12 +6,17 @@ compose_frames launch per chunk) and a single copy of the finished uint8 frames 
   python tools/animate.py --snapshot snapshot_latest.pth --sample-data sample_data.pickle --canonical canonical.npy \\
       --keys 0,7,19 --num 96 --orbit-turns 1 --out frames/        # PNGs frame_0000.png ... (PIL)
   python tools/animate.py ... --out walk.npy                      # one (num, S, S, 3) uint8 array
+  python tools/animate.py ... --parts --out parts/                 # the part segmentation in motion (render_part_animation)
+  python tools/animate.py ... --mesh-turntable field --out turn/   # the coloured mesh of the first key on a turntable
 
 The key poses, the camera and the bone lengths are entries of a sample_data.pickle (formats.read_sample_data; the
 camera and bone lengths of the first key); `--canonical` is the canonical pose (24, 4, 4) the model was trained with
 (the data set's canonical.npy). The generator is built from the options below with the shipping nerf_params
 (synth.nerf_config, a tri-plane per identity) and the snapshot's weights are loaded into it; keys the snapshot lacks
-are reported. `num` must be a multiple of the number of keys (with --no-loop: of the number of keys minus one)."""
+are reported. `num` must be a multiple of the number of keys (with --no-loop: of the number of keys minus one).
+`--parts` draws the frames in the colours of the part that owns each ray, over white. `--mesh-turntable field|parts`
+extracts the mesh of the first key once (HIP marching cubes), in the radiance field's colours or the part colours, and
+turns it through `--num` angles of one turn (render_mesh_turntable: HIP rasteriser and deferred shading per frame)."""
 import argparse
 import math
 import os
@@ -39,6 +44,13 @@ def main():
     ap.add_argument("--truncation-psi", type=float, default=0.4)
     ap.add_argument("--frames-per-batch", type=int, default=8)
     ap.add_argument("--black-background", action="store_true")
+    ap.add_argument("--parts", action="store_true", help="the part segmentation in place of the colour")
+    ap.add_argument("--mesh-turntable", choices=["field", "parts"], default=None,
+                    help="a turntable of the first key's coloured mesh in place of the march")
+    ap.add_argument("--voxel-size", type=float, default=0.003, help="mesh turntable: the density sweep's voxel")
+    ap.add_argument("--mesh-th", type=float, default=15.0, help="mesh turntable: the density threshold")
+    ap.add_argument("--unlit", action="store_true", help="mesh turntable: the colour itself, without the Phong terms")
+    ap.add_argument("--render-size", type=int, default=512, help="mesh turntable: the frames' size")
     ap.add_argument("--size", type=int, default=128)
     ap.add_argument("--z-dim", type=int, default=256)
     ap.add_argument("--nc", type=int, default=48)
@@ -68,8 +80,20 @@ def main():
     orbit = None
     if args.orbit_turns:
         orbit = torch.arange(args.num, dtype=torch.float64, device=dev) * (2 * math.pi * args.orbit_turns / args.num)
-    frames, _, _ = gen.render_animation(key_poses, bone_length, intrinsics, z, num=args.num, loop=not args.no_loop, orbit=orbit,
-                                        truncation_psi=args.truncation_psi, frames_per_batch=args.frames_per_batch)
+    if args.mesh_turntable:
+        angles = torch.arange(args.num, dtype=torch.float32, device=dev) * (2 * math.pi / args.num)
+        frames = gen.render_mesh_turntable(key_poses[:1].float(), intrinsics, z, bone_length, angles,
+                                           voxel_size=args.voxel_size, mesh_th=args.mesh_th,
+                                           truncation_psi=args.truncation_psi, color=args.mesh_turntable,
+                                           lit=not args.unlit, render_size=args.render_size)
+    elif args.parts:
+        frames, _, _ = gen.render_part_animation(key_poses, bone_length, intrinsics, z, num=args.num, loop=not args.no_loop,
+                                                 orbit=orbit, truncation_psi=args.truncation_psi,
+                                                 frames_per_batch=args.frames_per_batch)
+    else:
+        frames, _, _ = gen.render_animation(key_poses, bone_length, intrinsics, z, num=args.num, loop=not args.no_loop,
+                                            orbit=orbit, truncation_psi=args.truncation_psi,
+                                            frames_per_batch=args.frames_per_batch)
     frames = frames.cpu().numpy()                                       # the one device-to-host copy
     if args.out.endswith(".npy"):
         np.save(args.out, frames)

@@ -231,6 +231,45 @@ def export_ply(vertices, triangles, path: str, colors=None, labels=None) -> None
         fh.write(face.tobytes())
 
 
+def export_point_cloud(points, flags, path: str, colors=None, normals=None) -> None:
+    """Binary little-endian PLY of the valid pixels of ops.geometry_buffers: `points` (..., 3) and `flags` (...) (bit 0 =
+    valid) of one or several images; per vertex float x y z, with `normals` (..., 3) float nx ny nz, with `colors`
+    (..., 3) - uint8 as the shape image holds them, or floats in [0, 1] - uchar red green blue; no faces."""
+    import numpy as np
+    p = _host(points, np.float32)
+    keep = (_host(flags).astype(np.uint8) & 1).astype(bool)
+    if p.shape[-1:] != (3,) or p.shape[:-1] != keep.shape:
+        raise ValueError(f"export_point_cloud takes points (..., 3) and flags of the same leading shape, got {p.shape} and {keep.shape}")
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {int(keep.sum())}",
+              "property float x", "property float y", "property float z"]
+    if normals is not None:
+        n = _host(normals, np.float32)
+        if n.shape != p.shape:
+            raise ValueError(f"export_point_cloud takes normals of the points' shape {p.shape}, got {n.shape}")
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        header += ["property float nx", "property float ny", "property float nz"]
+    if colors is not None:
+        c = _host(colors)
+        if c.shape != p.shape:
+            raise ValueError(f"export_point_cloud takes colors of the points' shape {p.shape}, got {c.shape}")
+        if c.dtype != np.uint8:
+            with np.errstate(invalid="ignore"):
+                c = np.floor(255 * np.clip(np.nan_to_num(c.astype(np.float64), nan=0.0), 0, 1)).astype(np.uint8)
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        header += ["property uchar red", "property uchar green", "property uchar blue"]
+    header.append("end_header")
+    vert = np.zeros(int(keep.sum()), dtype=fields)
+    vert["x"], vert["y"], vert["z"] = p[keep].T
+    if normals is not None:
+        vert["nx"], vert["ny"], vert["nz"] = n[keep].T
+    if colors is not None:
+        vert["red"], vert["green"], vert["blue"] = c[keep].T
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(header) + "\n").encode("ascii"))
+        fh.write(vert.tobytes())
+
+
 def rasterize_mesh(vertices: torch.Tensor, triangles: torch.Tensor, intrinsics, img_size: int, render_size: int = 512):
     """render_mesh_'s image (mesh_rendering.py:17-47) on the device (libenarf_raster.so), without pytorch3d.
 

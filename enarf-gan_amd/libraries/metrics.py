@@ -29,3 +29,10 @@ def lpips(img1, img2):
 def neural_actor_lpips(img1, img2):
     from lpips_pytorch import LPIPS  # noqa: F401  (as above)
     raise ImportError("lpips_pytorch is installed but its AlexNet weights are not wired into this package")
+
+
+def inv_depth_mse(gen_disparity, gt_disparity):
+    """Mean squared error between generated and ground-truth inverse-depth maps of equal shape, as a Python float: what
+    the reference's evaluation/compute_depth.py:69-77 computes with MSELoss on the host, summed in fp64 on the device by
+    libenarf_geom.so (one host read). For a whole evaluation set keep an ops.DepthError and call result() once."""
+    return ops.DepthError().update(gen_disparity, gt_disparity).result()["inv_depth_mse"]

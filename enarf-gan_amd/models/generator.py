@@ -152,6 +152,17 @@ class TriNARFGenerator(_RendererShell):
         part_map = self.nerf.buffers_tensors["part_map"]
         return color.reshape(B, 3, S, S), part_map.reshape(B, S, S), mask.reshape(B, S, S)
 
+    def render_geometry(self, pose_to_camera, bone_length, z, inv_intrinsics, truncation_psi=1, shade="normal", **buffer_kwargs):
+        """The geometry of the frames forward() renders, from the march's own disparity: (image (B, S, S, 3) uint8 - the
+        shape image in `shade` = "normal", "lit" or "depth" -, the GeometryBuffers of ops.geometry_buffers (depth, points,
+        normals, flags, image), colour (B, 3, S, S), mask (B, S, S)), all on the device, one march and one launch more,
+        with no host synchronisation inside. Depth and points are metric, in the space of pose_to_camera and of
+        extract_mesh's vertices; buffer_kwargs go to ops.geometry_buffers (edge, mask_threshold, near, far, background,
+        want, ...)."""
+        z_nerf, z_render, _ = self._latent_parts(z)
+        return self.nerf.render_geometry(pose_to_camera, inv_intrinsics, z_nerf, z_render, bone_length, self.size,
+                                         truncation_psi=truncation_psi, shade=shade, **self._samples, **buffer_kwargs)
+
     def render_extracted_mesh(self, pose_to_camera, intrinsics, z, bone_length, voxel_size=0.003, mesh_th=15,
                               truncation_psi=0.4):
         """render_mesh built on the device (HIP marching cubes, HIP hard-Phong rasteriser): (image (512, 512, 3) uint8
@@ -232,6 +243,53 @@ class TriNARFGenerator(_RendererShell):
                 ops.compose_frames(color, alpha, background, return_masks=False, out=(frames[a:b], None))
                 part_maps[a:b] = nerf.buffers_tensors["part_map"].reshape(c, S, S)
         return frames, part_maps, poses
+
+    def render_geometry_animation(self, key_poses, bone_length, intrinsics, z, num=100, loop=True, orbit=None,
+                                  truncation_psi=0.4, frames_per_batch=8, background=1.0, shade="normal", **buffer_kwargs):
+        """render_animation of the geometry: (frames (num, S, S, 3) uint8 - the shape image of ops.geometry_buffers in
+        `shade` over `background` -, depth (num, S, S) fp32 in metric units, poses (num, J, 4, 4) in key_poses' dtype), all
+        device tensors, with no host synchronisation inside. The structure is render_part_animation's: one
+        interpolate_pose launch, one tri-plane, the frames marched frames_per_batch at a time, each chunk turned into
+        bytes and depths by one geometry_buffers launch that writes into frames[a:b] and depth[a:b]; frames_per_batch=1
+        gives the bytes of render_geometry on one frame. buffer_kwargs go to ops.geometry_buffers (edge, mask_threshold,
+        near, far, ...), except `want` and `out`, which this function sets itself: passing either raises ValueError."""
+        from .. import ops
+        from ..libraries.NeRF.rendering import render
+        taken = sorted(k for k in ("want", "out") if k in buffer_kwargs)
+        if taken:
+            raise ValueError(f"render_geometry_animation writes image and depth into its own tensors: {', '.join(taken)} "
+                             "cannot be passed")
+        if not (z.shape[0] == 1 and bone_length.shape[0] == 1):
+            raise AssertionError("render_geometry_animation takes one identity: z and bone_length of batch 1")
+        per = int(frames_per_batch)
+        if per < 1:
+            raise ValueError(f"render_geometry_animation: frames_per_batch {frames_per_batch} < 1")
+        nerf, S = self.nerf, self.size
+        with torch.no_grad():
+            poses, poses32 = ops.interpolate_pose(key_poses, nerf.parent_id, num, loop, orbit, return_f32=True)
+            dev, n_frames = poses.device, poses.shape[0]
+            z_nerf, z_render, _ = self._latent_parts(z)
+            tri = nerf.compute_tri_plane_feature(z_nerf, bone_length, truncation_psi)
+            K_inv = torch.linalg.inv_ex(torch.as_tensor(intrinsics).float().to(dev).reshape(-1, 3, 3)[:1]).inverse
+            _, pixels = self.ray_sampler(S, S, min(per, n_frames), device=dev)
+            frames = torch.empty((n_frames, S, S, 3), dtype=torch.uint8, device=dev)
+            depth = torch.empty((n_frames, S, S), dtype=torch.float32, device=dev)
+            mlp = nerf.mlp.as_dict()
+            for a in range(0, n_frames, per):
+                b = min(a + per, n_frames)
+                c = b - a
+                bl, z_rend = bone_length.expand(c, -1, -1), z_render.expand(c, -1)
+                parts, pack = ops.prepare(poses32[a:b], bl, nerf.canonical_bone_length, z_rend, mlp, nerf.parent_id,
+                                          nerf.origin_location, nerf.coordinate_scale)
+                model_input = {"z": z_nerf, "z_rend": z_rend, "bone_length": bl, "truncation_psi": truncation_psi,
+                               "tri_plane_feature": tri}
+                _, alpha, disparity = render(nerf, pixels[:c], poses32.new_empty(c, nerf.num_bone, 4, 4),
+                                             K_inv.expand(c, -1, -1), model_input=model_input, _parts=parts, _pack=pack,
+                                             **self._samples)
+                ops.geometry_buffers(disparity * nerf.coordinate_scale, alpha, K_inv, size=(S, S), shade=shade,
+                                     background=background, want=("depth", "image"),
+                                     out={"image": frames[a:b], "depth": depth[a:b]}, **buffer_kwargs)
+        return frames, depth, poses
 
     def render_animation(self, key_poses, bone_length, intrinsics, z, num=100, loop=True, orbit=None, truncation_psi=0.4,
                          frames_per_batch=8, black_bg_if_possible=False):
@@ -324,6 +382,19 @@ class DSONARFGenerator(_RendererShell):
                                  bone_length, return_intermediate=False, camera_pose=camera_pose, **self._samples)
         backdrop = -1 if background is None else background
         return color + backdrop * (1 - alpha[:, None]), alpha, ray_idx
+
+    def render_geometry(self, pose_to_camera, inv_intrinsics, frame_time, bone_length, camera_pose=None, render_size=128,
+                        shade="normal", bbox=None, **buffer_kwargs):
+        """The geometry of the frames render_entire_img renders, for every image of the batch: (image (B, H, W, 3) uint8,
+        the GeometryBuffers of ops.geometry_buffers, colour (B, 3, H, W), mask (B, H, W)) with (H, W) = render_size squared
+        or the rectangle bbox = (x0, y0, x1, y1); inv_intrinsics in pixels of the full frame. One march and one launch
+        more, no host synchronisation inside; depth and points are metric, in the space of pose_to_camera."""
+        z_tri, z_render = self.get_latents(frame_time, pose_to_camera)
+        size, origin = (render_size, render_size), (0, 0)
+        if bbox is not None:
+            size, origin = (bbox[3] - bbox[1], bbox[2] - bbox[0]), (bbox[0], bbox[1])
+        return self.nerf.render_geometry(pose_to_camera, inv_intrinsics, z_tri, z_render, bone_length, size, shade=shade,
+                                         origin=origin, camera_pose=camera_pose, **self._samples, **buffer_kwargs)
 
     def render_entire_img(self, pose_to_camera, inv_intrinsics, frame_time, bone_length, camera_pose=None,
                           render_size=128, semantic_map=False, use_normalized_intrinsics=False, no_grad=True, bbox=None):

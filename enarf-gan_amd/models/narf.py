@@ -327,6 +327,28 @@ class TriPlaneNARF(nn.Module):
         return render_entire_img(self, pose_parts, inv_intrinsics, camera_pose, render_size, Nc, Nf, semantic_map,
                                  use_normalized_intrinsics, no_grad, model_input, bbox=bbox)
 
+    @torch.no_grad()
+    def render_geometry(self, pose_to_camera, inv_intrinsics, z, z_rend, bone_length, size, truncation_psi=1, Nc=64, Nf=128,
+                        shade="normal", origin=(0, 0), step=1.0, camera_pose=None, **buffer_kwargs):
+        """The geometry of the frames forward() renders: one march, then one launch of ops.geometry_buffers on the march's
+        own disparity and mask. size = S or (H, W); pixel (r, c) is marched at x = origin[0] + (c + 0.5) step, y = origin[1] +
+        (r + 0.5) step, the rule geometry_buffers applies to the same inv_intrinsics. Returns (image (B, H, W, 3) uint8,
+        the GeometryBuffers, colour (B, 3, H, W), mask (B, H, W)). The disparity is brought back to metric units as
+        TriNARFGenerator.forward does (x coordinate_scale, one fp32 multiply), so depth and points are in the space of
+        pose_to_camera and of extract_mesh's vertices, and equal geometry_buffers of forward's own outputs bit for bit."""
+        H, W = (int(size), int(size)) if not hasattr(size, "__len__") else (int(size[0]), int(size[1]))
+        B, dev = pose_to_camera.shape[0], pose_to_camera.device
+        idx = torch.arange(H * W, device=dev)
+        x = (idx % W + 0.5).float() * step + origin[0]
+        y = (torch.div(idx, W, rounding_mode="floor") + 0.5).float() * step + origin[1]
+        pixels = torch.stack([x, y, torch.ones_like(x)], dim=0)[None, None].expand(B, -1, -1, -1).contiguous()
+        K_inv = torch.as_tensor(inv_intrinsics).float().to(dev)
+        color, mask, disparity = self.forward(B, pixels, pose_to_camera, K_inv, z, z_rend, bone_length, Nc=Nc, Nf=Nf,
+                                              truncation_psi=truncation_psi, camera_pose=camera_pose, return_disparity=True)
+        buffers = ops.geometry_buffers(disparity * self.coordinate_scale, mask, K_inv, size=(H, W), origin=origin, step=step,
+                                       shade=shade, **buffer_kwargs)
+        return buffers.image, buffers, color.reshape(B, 3, H, W), mask.reshape(B, H, W)
+
     def density_volume(self, pose_to_camera, z, z_rend, bone_length, voxel_size=0.003, truncation_psi=0.4):
         """The (2/voxel_size + 1)^3 density grid `render_mesh` thresholds (libraries/NARF/base.py:65-77 up to the
         marching-cubes call): one lattice-mode launch of the query kernel, the volume stays on the device."""

@@ -942,3 +942,28 @@ def shade_fragments(pix_to_face: torch.Tensor, bary: torch.Tensor, normals: torc
     from . import _paint_lib
     return _paint_lib.shade_fragments(pix_to_face, bary, normals, vertices, triangles, vertex_colors, vertex_labels, palette,
                                       lit, background, neutral)
+
+
+# ------------------------------------------------------------------------------------------------- geometry buffers
+from ._geom_lib import DepthError, GeometryBuffers  # noqa: E402,F401  (the running depth error; geometry_buffers' result)
+
+
+def geometry_buffers(disparity: torch.Tensor, mask: torch.Tensor, inv_intrinsics: torch.Tensor, *, size=None, origin=(0, 0),
+                     step=1.0, depth_scale=1.0, mask_threshold=0.5, edge=0.05, normalise=True, shade="normal", near=None,
+                     far=None, background=1.0, want=("depth", "points", "normals", "flags", "image"), out=None):
+    """The disparity and mask of a march to geometry, in one launch of libenarf_geom.so: the namedtuple GeometryBuffers
+    (depth (B, H, W) fp32, points (B, H, W, 3) fp32 in camera space, normals (B, H, W, 3) fp32, flags (B, H, W) uint8 with
+    bit 0 = valid and bit 1 = normal valid, image (B, H, W, 3) uint8); a field not named in `want` is None and is not
+    written. disparity and mask are (B, H, W), or (B, n) with size=(H, W); inv_intrinsics (3, 3), (1, 3, 3) or (B, 3, 3).
+    Pixel (r, c) sits at x = origin[0] + (c + 0.5) step, y = origin[1] + (r + 0.5) step. A pixel is valid when its mask is
+    at least mask_threshold and its disparity positive; depth = depth_scale mask / disparity (the march's disparity is not
+    divided by the mask), or depth_scale / disparity with normalise=False; point = depth K^-1 (x, y, 1). Normals come from
+    the differences of the 4-neighbours whose depth lies within `edge` (relative; negative = no test) of the pixel's, and
+    face the camera. shade: "normal" (0.5 + 0.5 (Nx, -Ny, -Nz)), "lit" (the rasteriser's hard-Phong terms on white) or
+    "depth" ((1 / z - 1 / far) / (1 / near - 1 / far)); pixels without what the mode needs take `background`, a number or
+    three. `out` maps names of `want` to contiguous tensors to write into. Computed in fp64 from the fp32 inputs,
+    bit-identical from run to run, nothing synchronises. ValueError for shapes, dtypes or values it does not take."""
+    from . import _geom_lib
+    return _geom_lib.geometry_buffers(disparity, mask, inv_intrinsics, size, origin, step, depth_scale, mask_threshold, edge,
+                                      normalise, shade, near, far, background, want, out)
+

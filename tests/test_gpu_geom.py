@@ -1,0 +1,378 @@
+"""GPU tests of libenarf_geom.so: geom_buffers_kernel against the float64 numpy restatement of its contract
+(tests/geom_reference.py) on hand-written buffers and on analytic scenes as batches, determinism and `want` subsets on
+poisoned outputs, the depth-error kernels against the referee's float64 sums, and the model-level entry points
+(render_geometry, render_geometry_animation, the inverse z-buffer of rasterize_mesh). The referee reads the very values
+the kernel reads, so no pixel is left out of any comparison."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import geom_cases as GC
+import geom_reference as GR
+
+pytestmark = pytest.mark.gpu
+
+FIELDS = ("depth", "points", "normals", "flags", "image")
+
+
+def _dev(a):
+    return torch.from_numpy(np.array(a)).cuda()              # a copy: the shared inputs are read-only
+
+
+def _buffers(q, m, K, **kw):
+    """ops.geometry_buffers on numpy inputs; the outputs as numpy"""
+    from enarf_gan_amd import ops
+    out = ops.geometry_buffers(_dev(q), _dev(m), _dev(K), **kw)
+    torch.cuda.synchronize()
+    assert out._fields == FIELDS
+    return {k: None if getattr(out, k) is None else getattr(out, k).cpu().numpy() for k in FIELDS}
+
+
+def _check(got, ref, what):
+    """flags exact; depth, points and normals the referee rounded to fp32, or one fp32 step from it (fp64 +, -, *, / and
+    sqrt rounded once each on both sides; only the last place of an fp64 operation can differ and move one rounding);
+    image within one level on every pixel"""
+    assert got["flags"].dtype == np.uint8 and got["image"].dtype == np.uint8 and got["depth"].dtype == np.float32, what
+    assert got["flags"].shape == ref["flags"].shape and got["image"].shape == ref["image"].shape, what
+    ulps = {k: GR.ulps_from(got[k], ref[k]) for k in ("depth", "points", "normals")}
+    d = np.abs(got["image"].astype(np.int16) - ref["image"].astype(np.int16))
+    print(f"{what}: " + ", ".join(f"{k} {u.max():.0f} ulp ({(u > 0).sum()} off)" for k, u in ulps.items())
+          + f", image {d.max()} levels ({(d > 0).sum()} off) of {d.size}, flags {(got['flags'] != ref['flags']).sum()} off")
+    assert np.array_equal(got["flags"], ref["flags"]), what
+    for k, u in ulps.items():
+        assert u.max() <= 1, (what, k)
+    assert d.max() <= 1, what
+
+
+# ------------------------------------------------------------------------------------------------- the kernel alone
+def test_hand_written_buffers_match_the_referee():
+    """the hand-written buffer of tests/geom_cases.py at 8 x 8 (a mask at the threshold and one step below, q = 0, q < 0,
+    NaN and inf, a NaN mask, one-sided differences at invalid neighbours and at the border) and the edge test at
+    equality; normalise on and off, the edge rule on and off, every shade mode"""
+    q, m, K = GC.hand_buffer(8)
+    for kw in (dict(), dict(edge=-1.0), dict(normalise=False, depth_scale=2.0), dict(shade="lit", background=(0.1, 0.2, 0.3)),
+               dict(shade="depth", near=1.0, far=3.0, background=0.0), dict(mask_threshold=1.5)):
+        got, ref = _buffers(q[None], m[None], K, **kw), GR.buffers(q[None], m[None], K, **kw)
+        _check(got, ref, f"hand buffer {kw}")
+    got = _buffers(q[None], m[None], K)
+    for pix in GC.HAND_INVALID:
+        assert got["flags"][0][pix] == 0 and got["depth"][0][pix] == 0 and (got["image"][0][pix] == 255).all()
+    assert got["flags"][0][1, 1] == 1 and got["flags"][0][2, 2] == 3 and got["flags"][0][0, 0] == 3
+    q, m, K, edge = GC.edge_equality()
+    got, ref = _buffers(q[None], m[None], K, edge=edge), GR.buffers(q[None], m[None], K, edge=edge)
+    _check(got, ref, "edge at equality")
+    # the right column has the pixel one step beyond the limit as its only vertical neighbour: no difference there
+    assert got["flags"][0].tolist() == [[3, 3, 1], [1, 3, 1], [3, 3, 1]]
+
+
+@functools.lru_cache(maxsize=None)
+def _batch(H, W, origin=(0.0, 0.0), step=1.0, which=0):
+    """B = 2 with two different inv_intrinsics: (scenes, disparity, mask (2, H, W), inv_intrinsics (2, 3, 3)); batch 0 is
+    the tilted plane and the sphere, batch 1 the sphere in front of a plane and the tilted plane under another focal length"""
+    kinds = (("plane", None), ("sphere", None)) if which == 0 else (("sphere_on_plane", None), ("plane", 45.0))
+    scenes = [GC.scene(kind, H, W, f=f, origin=origin, step=step) for kind, f in kinds]
+    return (scenes,) + tuple(np.stack([sc[k] for sc in scenes]) for k in ("disparity", "mask", "inv_intrinsics"))
+
+
+@pytest.mark.parametrize("H,W,kw", [(37, 53, dict()), (64, 64, dict(shade="lit")), (130, 17, dict(shade="depth", near=1.0, far=5.0)),
+                                    (37, 53, dict(origin=(3, 5), step=2.0, shade="lit", background=(0.2, 0.4, 0.6)))])
+def test_scenes_match_the_referee(H, W, kw):
+    """scenes 1 to 3 of tests/geom_cases.py in batches of two with a matrix per image; 37 x 53 and 130 x 17 leave partial
+    tiles on both axes and show a swap of H and W; one case samples every second pixel from (3, 5)"""
+    for which in (0, 1):
+        scenes, q, m, K = _batch(H, W, tuple(kw.get("origin", (0.0, 0.0))), kw.get("step", 1.0), which)
+        assert not np.array_equal(K[0], K[1])
+        got, ref = _buffers(q, m, K, **kw), GR.buffers(q, m, K, **kw)
+        _check(got, ref, f"scenes {H} x {W} batch {which} {kw}")
+        for b, sc in enumerate(scenes):                            # the kernel's own normals against the analytic ones
+            has = (got["flags"][b] & 2) > 0
+            assert has.sum() > 0.2 * H * W and np.median(GR.angle_deg(got["normals"][b][has], sc["normal"][has])) <= 0.5
+    # one shared matrix: (3, 3) and (1, 3, 3) give what B copies of it give
+    one, many = _buffers(q, m, K[0], **kw), _buffers(q, m, np.stack([K[0]] * 2), **kw)
+    assert all(one[k].tobytes() == many[k].tobytes() == _buffers(q, m, K[:1], **kw)[k].tobytes() for k in FIELDS)
+
+
+def test_background_only_and_single_pixel_images():
+    e = GC.scene("empty", 37, 53)
+    got = _buffers(e["disparity"][None], e["mask"][None], e["inv_intrinsics"], background=(1.0, 0.5, 0.0))
+    _check(got, GR.buffers(e["disparity"][None], e["mask"][None], e["inv_intrinsics"], background=(1.0, 0.5, 0.0)), "empty")
+    assert not got["flags"].any() and not got["depth"].any() and not got["normals"].any() and (got["image"] == [255, 127, 0]).all()
+    q, m, K = np.float32([[[0.5]]]), np.float32([[[1.0]]]), GC.pinhole_inverse(2.0, 1, 1)
+    for kw in (dict(), dict(shade="depth", near=1.0, far=4.0)):
+        got, ref = _buffers(q, m, K, **kw), GR.buffers(q, m, K, **kw)
+        _check(got, ref, f"1 x 1 {kw}")
+    assert got["flags"].tolist() == [[[1]]] and got["depth"].tolist() == [[[2.0]]] and got["points"][0, 0, 0].tolist() == [0.0, 0.0, 2.0]
+    assert (got["image"] == int(255 * ((0.5 - 0.25) / 0.75))).all()
+    flat = _buffers(np.float32([[0.5] * 6]), np.float32([[1.0] * 6]), GC.pinhole_inverse(2.0, 2, 3), size=(2, 3))     # (B, n) with size
+    assert flat["depth"].shape == (1, 2, 3) and (flat["depth"] == 2).all() and (flat["flags"] == 3).all()
+
+
+def test_two_calls_are_bit_identical_and_want_writes_nothing_else():
+    from enarf_gan_amd import ops
+    _, q, m, K = _batch(37, 53)
+    a, b = _buffers(q, m, K, shade="lit"), _buffers(q, m, K, shade="lit")
+    for k in FIELDS:
+        assert a[k].tobytes() == b[k].tobytes(), k
+    dq, dm, dK = _dev(q), _dev(m), _dev(K)
+    shapes = dict(depth=(2, 37, 53), points=(2, 37, 53, 3), normals=(2, 37, 53, 3), flags=(2, 37, 53), image=(2, 37, 53, 3))
+    for want in (("depth",), ("image",), ("normals", "flags"), ("points", "image")):
+        # every output is given, poisoned, in one allocation with a guard band on both sides of each; only `want` may change
+        sizes = {k: int(np.prod(shapes[k])) * (1 if k in ("flags", "image") else 4) for k in FIELDS}
+        arena = torch.full((sum(sizes.values()) + 64 * 6,), 0xA5, dtype=torch.uint8, device="cuda")
+        views, at = {}, 64
+        for k in FIELDS:
+            raw = arena[at:at + sizes[k]]
+            views[k] = (raw if k in ("flags", "image") else raw.view(torch.float32)).view(shapes[k])
+            at += sizes[k] + 64
+        out = ops.geometry_buffers(dq, dm, dK, shade="lit", want=want, out={k: views[k] for k in want})
+        torch.cuda.synchronize()
+        assert all((getattr(out, k) is None) == (k not in want) for k in FIELDS)
+        before = arena.cpu().numpy().copy()
+        for k in want:
+            assert getattr(out, k).data_ptr() == views[k].data_ptr()
+            assert views[k].cpu().numpy().tobytes() == a[k].tobytes(), (want, k)
+            views[k].view(-1).view(torch.uint8).fill_(0xA5)
+        torch.cuda.synchronize()
+        assert (arena.cpu().numpy() == 0xA5).all() and (before != 0xA5).any(), want
+
+
+# ------------------------------------------------------------------------------------------------- the depth error
+def _ulp32(got, ref):
+    return float(GR.ulps_from(np.float32(got), np.float64(ref)))
+
+
+@pytest.mark.parametrize("shape", [(3, 37, 53), (1, 1, 1)])
+@pytest.mark.parametrize("with_mask", [True, False])
+def test_depth_error_matches_the_referee_and_repeats_bit_for_bit(shape, with_mask):
+    """two updates; counts exact, each sum within one fp32 ulp of the float64 referee's once both are rounded to fp32
+    (n <= 2^14 non-negative terms: a relative fp64 error below n 2^-53, far below 2^-24); a second run gives the same bits"""
+    from enarf_gan_amd import ops
+    from enarf_gan_amd.libraries.metrics import inv_depth_mse
+    batches = [GC.error_batch(shape, seed) for seed in (11, 12)]
+    ref = GR.merge([GR.depth_error(q, g, m if with_mask else None) for q, g, m in batches])
+
+    def run():
+        err = ops.DepthError()
+        for q, g, m in batches:
+            assert err.update(_dev(q), _dev(g), _dev(m) if with_mask else None) is err
+        return err, err.state().cpu().numpy().tobytes()
+
+    err, bits = run()
+    got = err.result()
+    print(f"depth error {shape} mask={with_mask}: {got}")
+    for k in ("n", "n_fg", "inter", "union"):
+        assert got[k] == ref[k], k
+    assert got["updates"] == 2 and got["n"] == 2 * int(np.prod(shape))
+    for k in ("sse_all", "sse_fg"):
+        assert _ulp32(got[k], ref[k]) <= 1, (k, got[k], ref[k])
+    assert got["inv_depth_mse"] == got["sse_all"] / got["n"] and _ulp32(got["inv_depth_mse"], ref["inv_depth_mse"]) <= 1
+    assert got["iou"] == got["inter"] / got["union"] if got["union"] else np.isnan(got["iou"])
+    assert run()[1] == bits
+    err.reset()
+    assert err.result()["n"] == 0 and err.result()["sse_all"] == 0 and err.result()["updates"] == 0
+    q, g, _ = batches[0]
+    one = inv_depth_mse(_dev(q), _dev(g))
+    want = GR.depth_error(q, g)
+    assert _ulp32(one, want["sse_all"] / want["n"]) <= 1
+
+
+def test_depth_error_over_many_workgroups_and_non_finite_values():
+    """2^21 + 3 pixels: the full 1024 records and a grid-stride loop with a ragged end; then a NaN propagates as in MSELoss"""
+    from enarf_gan_amd import ops
+    q, g, m = GC.error_batch((2 ** 21 + 3,), 13)
+    ref = GR.depth_error(q, g, m)
+    got = ops.DepthError().update(_dev(q), _dev(g), _dev(m)).result()
+    assert all(got[k] == ref[k] for k in ("n", "n_fg", "inter", "union"))
+    assert _ulp32(got["sse_all"], ref["sse_all"]) <= 1 and _ulp32(got["sse_fg"], ref["sse_fg"]) <= 1
+    q[5] = np.nan
+    got = ops.DepthError().update(_dev(q), _dev(g), _dev(m)).result()
+    assert np.isnan(got["sse_all"]) and np.isnan(got["inv_depth_mse"]) and got["n"] == q.size and got["union"] == ref["union"]
+
+
+def test_a_depth_error_belongs_to_one_stream():
+    from enarf_gan_amd import ops
+    q, g, m = (_dev(a) for a in GC.error_batch((2, 16, 16), 14))
+    err = ops.DepthError().update(q, g, m)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        with pytest.raises(ValueError, match="one stream"):
+            err.update(q, g, m)
+        other = ops.DepthError().update(q, g, m)                  # an object of its own on the side stream is fine
+    side.synchronize()
+    err.update(q, g, m)
+    assert err.result()["updates"] == 2 and other.result()["updates"] == 1
+    assert other.result()["sse_all"] * 2 == err.result()["sse_all"]
+
+
+# ------------------------------------------------------------------------------------------------- the model's entry points
+def _model():
+    from test_gpu_paint import _model
+    return _model()
+
+
+def test_render_geometry_is_geometry_buffers_of_forward():
+    """the buffers of render_geometry are ops.geometry_buffers of forward(return_disparity=True)'s own mask and disparity
+    (metric units) with depth_scale 1: the unit handling is fixed here. The sampler's seeds come from torch's generator,
+    reseeded before each route."""
+    from enarf_gan_amd import ops
+    gen, s, z, pose, bl, K, _ = _model()
+    S, psi = gen.size, 0.4
+    K_inv = torch.linalg.inv_ex(K.float()).inverse
+    for shade, kw in (("normal", dict()), ("lit", dict(edge=0.1, background=0.0)), ("depth", dict(near=1.0, far=6.0))):
+        torch.manual_seed(7)
+        image, buffers, color, mask = gen.render_geometry(pose, bl, z, K_inv, truncation_psi=psi, shade=shade, **kw)
+        torch.manual_seed(7)
+        fwd_image, fwd_mask, disparity = gen(pose, None, bl, z, K_inv, truncation_psi=psi, return_disparity=True)
+        want = ops.geometry_buffers(disparity, fwd_mask.reshape(1, -1), K_inv, size=(S, S), shade=shade, **kw)
+        assert image.shape == (1, S, S, 3) and image.dtype == torch.uint8 and image.data_ptr() == buffers.image.data_ptr()
+        assert torch.equal(mask, fwd_mask) and color.shape == (1, 3, S, S) and torch.equal(color - (1 - mask[:, None]), fwd_image)
+        for k in FIELDS:
+            assert torch.equal(getattr(buffers, k), getattr(want, k)), (shade, k)
+    flags = buffers.flags.cpu().numpy()
+    assert 0.05 < (flags & 1).mean() < 0.9 and (flags & 2).sum() > 0.5 * (flags & 1).sum()
+    # metric units: the valid points lie in front of the camera, around the root joint's translation
+    pts = buffers.points[0][buffers.flags[0] & 1 > 0]
+    assert float((pts.mean(0) - pose[0, 0, :3, 3]).norm()) < 1.0 and float(pts[:, 2].min()) > 0
+
+
+def test_geometry_animation_frames_are_single_renders():
+    """frames_per_batch = 1: frame i is, byte for byte, the shape image of render_geometry on pose i, and its depth map"""
+    from enarf_gan_amd import ops
+    from enarf_gan_amd.libraries.NARF.pose_utils import rotate_pose_by_angle
+    gen, s, z, pose, bl, K, _ = _model()
+    S, num, psi = gen.size, 4, 0.4
+    first = s["pose_to_camera"][:1]
+    keys = torch.cat([first, rotate_pose_by_angle(first, torch.tensor([0.7]))]).double().cuda()
+    torch.manual_seed(5)
+    frames, depth, poses = gen.render_geometry_animation(keys, bl, K, z, num=num, loop=False, truncation_psi=psi,
+                                                         frames_per_batch=1, shade="lit")
+    assert frames.shape == (num, S, S, 3) and frames.dtype == torch.uint8 and frames.is_cuda
+    assert depth.shape == (num, S, S) and depth.dtype == torch.float32
+    assert torch.equal(poses, ops.interpolate_pose(keys, s["parents"], num, False))
+    K_inv = torch.linalg.inv_ex(K.float()).inverse
+    torch.manual_seed(5)
+    for f in range(num):
+        image, buffers, _, _ = gen.render_geometry(poses[f:f + 1].float(), bl, z, K_inv, truncation_psi=psi, shade="lit")
+        assert torch.equal(frames[f], image[0]), f"frame {f}"
+        assert torch.equal(depth[f], buffers.depth[0]), f"depth of frame {f}"
+    assert not torch.equal(frames[0], frames[3]) and float((depth[0] > 0).float().mean()) > 0.05
+    torch.manual_seed(5)
+    chunked = gen.render_geometry_animation(keys, bl, K, z, num=num, loop=False, truncation_psi=psi, frames_per_batch=3)
+    assert chunked[0].shape == frames.shape and chunked[1].shape == depth.shape and torch.equal(chunked[2], poses)
+    with pytest.raises(AssertionError):
+        gen.render_geometry_animation(keys, bl, K, z.expand(2, -1), num=num)
+    for kw in (dict(want=("depth",)), dict(out={})):              # it writes into its own tensors: these two are not forwarded
+        with pytest.raises(ValueError, match="cannot be passed"):
+            gen.render_geometry_animation(keys, bl, K, z, num=num, **kw)
+
+
+def test_inverse_zbuf_gives_back_the_zbuf():
+    """normalise=False on 1 / zbuf of rasterize_mesh: the depth is the z-buffer within one fp32 step on covered pixels, and
+    the screen-space normals agree with the rasteriser's interpolated ones"""
+    import paint_cases as PC
+    from enarf_gan_amd import ops
+    from enarf_gan_amd.libraries.NARF.mesh_rendering import rasterize_mesh
+    verts, tris = PC.sphere()
+    R, (img, fx, fy, cx, cy) = 64, PC.CAMERAS[64]
+    K = PC.intrinsics(R)
+    f = rasterize_mesh(_dev(verts), _dev(tris), _dev(K).reshape(1, 3, 3), img, R)
+    covered = f.pix_to_face >= 0
+    inv = torch.where(covered, 1 / f.zbuf, torch.zeros_like(f.zbuf))
+    # pixel (r, c) of the R x R render is the point ((c + 0.5) img / R, (r + 0.5) img / R) of K's image
+    K_inv = torch.linalg.inv_ex(_dev(K)).inverse
+    out = ops.geometry_buffers(inv[None], covered.float()[None], K_inv, step=img / R, normalise=False)
+    torch.cuda.synchronize()
+    cov = covered.cpu().numpy()
+    assert cov.sum() > 500 and np.array_equal(out.flags[0].cpu().numpy() & 1, cov.astype(np.uint8))
+    steps = GR.ulps_from(out.depth[0].cpu().numpy()[cov], f.zbuf.cpu().numpy()[cov].astype(np.float64))
+    print(f"depth from 1 / zbuf: largest distance {steps.max():.0f} fp32 steps, {(steps > 0).sum()} of {cov.sum()} off")
+    assert steps.max() <= 1
+    has = (out.flags[0].cpu().numpy() & 2) > 0
+    n = f.normals.cpu().numpy()[has]
+    ang = GR.angle_deg(out.normals[0].cpu().numpy()[has], n / np.linalg.norm(n, axis=-1, keepdims=True))
+    print(f"screen-space normals against the rasteriser's: median {np.median(ang):.2f} deg over {has.sum()} pixels")
+    assert has.sum() > 400 and np.median(ang) < 5.0
+
+
+def test_inverse_depth_error_is_the_depth_error_of_forward():
+    """models/evaluate.inverse_depth_error on two hand-made batches of two, num_sample = 3 (the last batch is cut to one
+    sample): its result equals, figure for figure, a DepthError fed by forward(return_disparity=True) on the same samples
+    with the latents drawn from an equally seeded generator and the sampler's seeds from torch's, reseeded before each
+    route; the generator comes back in the mode it went in; too few samples raise"""
+    from enarf_gan_amd import ops
+    from enarf_gan_amd.libraries.NARF.pose_utils import rotate_pose_by_angle
+    from enarf_gan_amd.models.evaluate import inverse_depth_error
+    gen, s, _, _, _, _, _ = _model()
+    S, psi = gen.size, 0.4
+    first = s["pose_to_camera"][:1]
+    poses = torch.cat([first, rotate_pose_by_angle(first, torch.tensor([0.5]))]).float()
+    batches = [{"pose_3d": poses, "pose_3d_world": poses, "bone_length": s["bone_length"][:1].expand(2, -1, -1).contiguous(),
+                "intrinsics": s["intrinsics"][:1].expand(2, -1, -1).contiguous(),
+                "img": torch.from_numpy(GC.error_batch((2, S, S), seed)[1])} for seed in (21, 22)]
+    assert not gen.training
+    torch.manual_seed(9)
+    got = inverse_depth_error(gen, batches, 3, truncation_psi=psi, generator=torch.Generator(device="cuda").manual_seed(4))
+    assert not gen.training
+    torch.manual_seed(9)
+    latents, err = torch.Generator(device="cuda").manual_seed(4), ops.DepthError()
+    gen.train()
+    try:
+        with torch.no_grad():
+            for batch, take in zip(batches, (2, 1)):
+                on = lambda k: batch[k][:take].cuda()
+                z = torch.randn(take, 3 * gen.config.z_dim, device="cuda", generator=latents)
+                _, mask, disparity = gen(on("pose_3d"), None, on("bone_length"), z, torch.linalg.inv_ex(on("intrinsics")).inverse,
+                                         return_disparity=True, truncation_psi=psi)
+                err.update(disparity.reshape(take, S, S).contiguous(), on("img"), mask.reshape(take, S, S).contiguous())
+    finally:
+        gen.eval()
+    want = err.result()
+    print(f"inverse_depth_error: {got}")
+    assert got == want and got["n"] == 3 * S * S and got["updates"] == 2 and got["n_fg"] > 0 and 0 < got["iou"] < 1
+    gen.train()
+    try:
+        with pytest.raises(ValueError, match="hold 4 samples"):
+            inverse_depth_error(gen, batches, 5, truncation_psi=psi)
+        assert gen.training                                         # put back, also on the way out of an error
+    finally:
+        gen.eval()
+    with pytest.raises(ValueError, match="num_sample"):
+        inverse_depth_error(gen, batches, 0)
+
+
+def test_dso_render_geometry_maps_a_bbox_to_size_and_origin():
+    """DSONARFGenerator.render_geometry with bbox = (x0, y0, x1, y1): the buffers have (y1 - y0, x1 - x0) pixels, every valid
+    point projects through K to the centre of its own pixel of the full frame, (x0 + c + 0.5, y0 + r + 0.5), and mask and
+    depth are those of render_entire_img on the same rectangle (another route to the same march: compared at the
+    project's parity tolerance, in metric units)"""
+    from _helpers import Scene
+    from test_gpu_api import _dso_generator
+    S = 64
+    sc = Scene(S, 1, "center_fixed", 20)
+    gen, s = _dso_generator(sc, S), sc.raw
+    ft = torch.tensor([0.37]).cuda()
+    pose, bl, K_inv = s["pose_to_camera"].cuda(), s["bone_length"].cuda(), s["inv_intrinsics"].cuda()
+    x0, y0, W, H = 8, 16, 48, 32
+    bbox = (x0, y0, x0 + W, y0 + H)
+    torch.manual_seed(3)
+    image, buffers, color, mask = gen.render_geometry(pose, K_inv, ft, bl, None, S, shade="lit", bbox=bbox)
+    assert image.shape == (1, H, W, 3) and buffers.depth.shape == (1, H, W) and color.shape == (1, 3, H, W) and mask.shape == (1, H, W)
+    valid = buffers.flags[0] & 1 > 0
+    assert int(valid.sum()) > 100
+    K = torch.linalg.inv_ex(K_inv[0].double()).inverse
+    pix = buffers.points[0].double() @ K.T
+    pix = pix[..., :2] / pix[..., 2:]
+    r, c = torch.meshgrid(torch.arange(H, device="cuda"), torch.arange(W, device="cuda"), indexing="ij")
+    want = torch.stack([x0 + c + 0.5, y0 + r + 0.5], -1).double()
+    assert float((pix - want)[valid].abs().max()) < 1e-3
+    torch.manual_seed(3)
+    _, ref_mask, ref_disp = gen.render_entire_img(pose, K_inv, ft, bl, None, S, bbox=bbox)
+    assert float((mask[0] - ref_mask).abs().max()) < 1e-4
+    both = valid & (ref_mask >= 0.5) & (ref_disp > 0)
+    ref_depth = ref_mask / (ref_disp * gen.nerf.coordinate_scale)
+    assert int(both.sum()) > 100 and float(((buffers.depth[0] - ref_depth).abs() / ref_depth)[both].max()) < 1e-3
+    full = gen.render_geometry(pose, K_inv, ft, bl, None, S)[1]                 # no bbox: the whole render_size frame
+    assert full.depth.shape == (1, S, S)

@@ -8,6 +8,7 @@ compose_frames launch per chunk) and a single copy of the finished uint8 frames 
   python tools/animate.py ... --out walk.npy                      # one (num, S, S, 3) uint8 array
   python tools/animate.py ... --parts --out parts/                 # the part segmentation in motion (render_part_animation)
   python tools/animate.py ... --mesh-turntable field --out turn/   # the coloured mesh of the first key on a turntable
+  python tools/animate.py ... --geometry normal --out shape/       # the march's own geometry in motion (render_geometry_animation)
 
 The key poses, the camera and the bone lengths are entries of a sample_data.pickle (formats.read_sample_data; the
 camera and bone lengths of the first key); `--canonical` is the canonical pose (24, 4, 4) the model was trained with
@@ -16,7 +17,9 @@ camera and bone lengths of the first key); `--canonical` is the canonical pose (
 are reported. `num` must be a multiple of the number of keys (with --no-loop: of the number of keys minus one).
 `--parts` draws the frames in the colours of the part that owns each ray, over white. `--mesh-turntable field|parts`
 extracts the mesh of the first key once (HIP marching cubes), in the radiance field's colours or the part colours, and
-turns it through `--num` angles of one turn (render_mesh_turntable: HIP rasteriser and deferred shading per frame)."""
+turns it through `--num` angles of one turn (render_mesh_turntable: HIP rasteriser and deferred shading per frame).
+`--geometry normal|lit|depth` draws the shape the march itself carries - the normal map, a lit white surface, or the
+inverse depth between `--depth-range` - from the disparity of each frame (ops.geometry_buffers, no mesh extracted)."""
 import argparse
 import math
 import os
@@ -45,6 +48,9 @@ def main():
     ap.add_argument("--frames-per-batch", type=int, default=8)
     ap.add_argument("--black-background", action="store_true")
     ap.add_argument("--parts", action="store_true", help="the part segmentation in place of the colour")
+    ap.add_argument("--geometry", choices=["normal", "lit", "depth"], default=None,
+                    help="the shape image of the march's depth in place of the colour")
+    ap.add_argument("--depth-range", default="1.0,5.0", help="--geometry depth: near,far in the poses' units")
     ap.add_argument("--mesh-turntable", choices=["field", "parts"], default=None,
                     help="a turntable of the first key's coloured mesh in place of the march")
     ap.add_argument("--voxel-size", type=float, default=0.003, help="mesh turntable: the density sweep's voxel")
@@ -86,6 +92,12 @@ def main():
                                            voxel_size=args.voxel_size, mesh_th=args.mesh_th,
                                            truncation_psi=args.truncation_psi, color=args.mesh_turntable,
                                            lit=not args.unlit, render_size=args.render_size)
+    elif args.geometry:
+        near, far = (float(v) for v in args.depth_range.split(","))
+        frames, _, _ = gen.render_geometry_animation(key_poses, bone_length, intrinsics, z, num=args.num,
+                                                     loop=not args.no_loop, orbit=orbit, truncation_psi=args.truncation_psi,
+                                                     frames_per_batch=args.frames_per_batch, shade=args.geometry,
+                                                     near=near, far=far)
     elif args.parts:
         frames, _, _ = gen.render_part_animation(key_poses, bone_length, intrinsics, z, num=args.num, loop=not args.no_loop,
                                                  orbit=orbit, truncation_psi=args.truncation_psi,

@@ -198,8 +198,9 @@ def device_status(clear: bool = True) -> int:
 def raise_on_device_status(what: str) -> None:
     flags = device_status(clear=True)
     if flags & STATUS_MARCH_WATCHDOG:
-        raise EnarfHipError(f"{what}: an earlier enarf_render_fwd launch on this device was abandoned by its scheduler "
-                            "watchdog (ENARF_STATUS_MARCH_WATCHDOG): the outputs of that launch are incomplete")
+        raise EnarfHipError(f"{what}: an earlier enarf_render_fwd launch on this device was abandoned by a march watchdog "
+                            "(ENARF_STATUS_MARCH_WATCHDOG: the task march's scheduler, or the ray march's hand-off of a "
+                            "ray's fine tiles): the outputs of that launch are incomplete")
     if flags:
         raise EnarfHipError(f"{what}: device status {flags:#x}")
 

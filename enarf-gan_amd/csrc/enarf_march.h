@@ -136,8 +136,9 @@ __device__ __forceinline__ int build_cand_list(int *list, uint32_t set, int lane
 __device__ __forceinline__ int xcc_id() {
     return (int)(__builtin_amdgcn_s_getreg((20) | (0 << 6) | (3 << 11)) & 0xF);   // HW_REG_XCC_ID[3:0]
 }
-// LDS of the queue (ints, 16-byte aligned): 2 slots x [ray id, -, -, -, RayRec (8)], the kQueues x kClasses list lengths,
-// the cursor (band, tries, class)
+// LDS of the queue (ints, 16-byte aligned): 2 slots x [ray id, give-up flag, -, -, RayRec (8)], the kQueues x kClasses list
+// lengths, the cursor (band, tries, class). The give-up flag is the caller's (render_kernel's hand-off watchdog): it sits
+// beside the id so that the one load every wave makes per ray brings it along.
 constexpr int kQSlotInts = 12;
 constexpr int kQCountsOff = 2 * kQSlotInts;
 constexpr int kQCursorOff = kQCountsOff + kQueues * kClasses;
@@ -197,6 +198,10 @@ struct RayQueue {
     }
     // every thread, after a barrier that follows pop(slot)
     __device__ __forceinline__ int get(int slot) const { return l_q[slot * kQSlotInts]; }
+    // the same with the give-up flag beside the id, in one 8-byte load: {ray id, flag}
+    __device__ __forceinline__ int2 get_with_flag(int slot) const { return *reinterpret_cast<const int2 *>(l_q + slot * kQSlotInts); }
+    // ONE thread: zero / raise the flag of both slots (whichever slot the next get_with_flag reads)
+    __device__ __forceinline__ void set_flag(int v) { l_q[1] = v; l_q[kQSlotInts + 1] = v; }
     __device__ __forceinline__ RayRec rec(int slot) const { return *reinterpret_cast<const RayRec *>(l_q + slot * kQSlotInts + 4); }
 };
 
@@ -221,14 +226,16 @@ constexpr int SL_FBITS = SL_FH + 4 * kMaxSamples;
 constexpr int SL_FWMAX = SL_FBITS + kMaxSamples;
 constexpr int kSlotWords = SL_FWMAX + kMaxSamples;      // 1344 words = 5376 B
 static_assert(kSlotWords % 4 == 0 && SL_REC % 4 == 0 && SL_NEXT_REC % 4 == 0, "slot alignment");
+static_assert(kQSlotInts % 2 == 0, "RayQueue::get_with_flag loads 8 aligned bytes");
 
 // scratch section of the dynamic LDS (floats): render_kernel's [ray record][Nc + 1 bin edges][4 waves x 32 candidate ids]
-// [RayQueue ints]
+// [RayQueue ints][fine_done: render_kernel's count of finished fine passes, one per wave and ray]
 constexpr int SC_SLOT = 0;
 constexpr int SC_BTAB = SC_SLOT + kSlotWords;
 constexpr int SC_CAND = SC_BTAB + (kMaxSamples + 1 + 3) / 4 * 4;
 constexpr int SC_QUEUE = SC_CAND + 4 * 32;
-constexpr int kScratchFloats = SC_QUEUE + (kQueueLdsInts + 3) / 4 * 4;
+constexpr int SC_FINE_DONE = SC_QUEUE + (kQueueLdsInts + 3) / 4 * 4;
+constexpr int kScratchFloats = SC_FINE_DONE + 4;
 static_assert(SC_BTAB % 4 == 0 && SC_QUEUE % 4 == 0 && kScratchFloats % 4 == 0, "16-byte aligned scratch sections");
 template <int MODE>
 __host__ __device__ constexpr int lds_total_floats(int P) {

@@ -654,11 +654,20 @@ static_assert(kRenderWavesPerSimd * 4 * lds_total_floats<ENARF_MLP_F32>(ENARF_MA
               kRenderWavesPerSimd * 4 * lds_total_floats<ENARF_MLP_BF16>(ENARF_MAX_PARTS) <= 160 * 1024, "render_kernel's LDS");
 // priority of the one wave that runs S2 while the three others wait at the next barrier for it
 constexpr int kS2Prio = 3;
+// The wave that composites a ray polls the count of finished fine passes every ~0.1 us; the longest legitimate wait is one
+// fine tile (microseconds). 2^21 polls without the count arriving means the hand-off is broken: the wave raises the ray
+// queue's give-up flag, the device's sticky status word and counters[7], and every wave leaves the loop after the next S1
+// barrier instead of hanging the GPU (as march_kernel's watchdog does, kIdleLimit).
+constexpr unsigned kHandoffLimit = 1u << 21;
+// The device pointer of the sticky status word (host::status_word), written on the stream ahead of a device's first launch.
+// march_kernel takes it as a kernel parameter; render_kernel's signature is the key of its entry in the kernel -> tests
+// registry (tests/kernel_coverage.py) and stays the argument struct alone.
+__device__ unsigned int *g_status_word = nullptr;
 
 // SPL = samples per lane in the lane = sample stages: 1 for Nc, Nf <= 64, 2 up to 128 (each wave then loops over two
 // 16-sample tiles per pass). The stages are those of march_kernel (enarf_tasks.h) on ONE ray record in the scratch
-// section; what is this kernel's own is their schedule: which wave takes which tile, which wave runs S2 and S4, the three
-// barriers per ray, the pops and the restaging of the image context.
+// section; what is this kernel's own is their schedule: which wave takes which tile, which wave runs S2 and S4, the two
+// barriers and the counted hand-off per ray, the pops and the restaging of the image context.
 template <int MODE, int SPL>
 __global__ __launch_bounds__(256, kRenderWavesPerSimd) void render_kernel(const enarf_render_args a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -696,10 +705,15 @@ __global__ __launch_bounds__(256, kRenderWavesPerSimd) void render_kernel(const 
     S.H = a.H; S.W = a.W; S.P = P; S.mult_w = a.multiply_density_with_weight ? (a.uniform_part_weight ? 2 : 1) : 0;
     S.clamp_mask = a.clamp_mask; S.uniform_w = a.uniform_part_weight ? 1.0f / (float)P : 0.0f;
     int *l_cand = reinterpret_cast<int *>(scratch + SC_CAND) + wave * 32;
+    // fine passes finished in this workgroup: every wave adds 1 per ray, so 4 x (rays done) once a ray's fine tiles are
+    // complete; only ever counts up (a launch has fewer than 2^31 rays)
+    unsigned *l_fine_done = reinterpret_cast<unsigned *>(scratch + SC_FINE_DONE);
+    if (tid == 0) { *l_fine_done = 0u; rq.set_flag(0); }
     __syncthreads();                          // the staged image context is complete before any wave starts a tile
 
     MarchCounters C{0u, 0u, 0u, 0u, 0u};
     int qslot = 0;
+    unsigned fine_target = 0u;                // the count that says "every fine tile of the current ray is done"
 
     while (cur >= 0) {
         const uint32_t rid = (uint32_t)cur;
@@ -743,8 +757,12 @@ __global__ __launch_bounds__(256, kRenderWavesPerSimd) void render_kernel(const 
         for (int s = 0; s < SPL; ++s) usort[s] = 0.0f;
         if (wave == spare_wave && !a.bins) draw_sorted_uniforms<SPL>(a, rid, Nf, lane, usort);
         __syncthreads();
-        const int next_ray = rq.get(qslot ^ 1);
+        const int2 popped = rq.get_with_flag(qslot ^ 1);
+        const int next_ray = popped.x;
         qslot ^= 1;
+        // the hand-off watchdog fired in the previous ray's S4 (never expected): uniform here, because that wave raised the
+        // flag before it came to this barrier and nobody raises it between this barrier and the next
+        if (popped.y) break;
 
         // ---- S2 on ONE wave: the result goes through LDS; the other waves wait at the barrier instead of spending the
         // same ~350 VALU instructions each (the SIMDs are shared with two other workgroups that can use the slots).
@@ -766,14 +784,51 @@ __global__ __launch_bounds__(256, kRenderWavesPerSimd) void render_kernel(const 
                 ray_tile<MODE>(a, S, l_btab, l_cand, ncand, sw, seg, true, t, lane, C);
             }
         }
-        __syncthreads();
+        // ---- hand-off S3 -> S4 by count, not by a barrier: "all fine tiles of this ray are done" has ONE consumer, the wave
+        // that composites it. Every wave (with or without a fine tile) releases its tile's results and counts itself in;
+        // the three others go straight on to their coarse tile of the next ray, so the workgroup waits once per ray - at
+        // the next S1 barrier, for the longest fine + coarse pair - instead of for the longest fine tile here and the
+        // longest coarse tile there.
+        lds_release();
+        if (lane == 0) __hip_atomic_fetch_add(l_fine_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        fine_target += 4u;
 
         // ---- S4 on one wave, while the other waves are already in the next ray's coarse pass - on the wave that has no
-        // coarse tile there, when there is one.
+        // coarse tile there, when there is one (otherwise wave 0, before its coarse tile; also the last ray's S4, whose
+        // three other waves have counted themselves in before they left the kernel).
         const int s4_wave = (next_ray >= 0 && 3 * SPL * 16 >= Nc) ? ((3 - (next_ray & 3)) & 3) : 0;
-        if (wave == s4_wave) ray_composite_stage<SPL>(a, sw, rid, rec.dmin, rec.dmax, S.mult_w, lane);
-        // no barrier needed here: coarse arrays are rewritten in S1' (after this ray's S3 barrier, which follows every
-        // wave's S2 reads), fine arrays in S3' (after the S1' barrier, which wave 0 reaches only after this S4).
+        if (wave == s4_wave) {
+            unsigned polls = 0u;
+            bool complete = true;
+            // relaxed polls, one acquire at the end
+            while ((unsigned)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(l_fine_done, __ATOMIC_RELAXED,
+                                                                                    __HIP_MEMORY_SCOPE_WORKGROUP)) < fine_target) {
+                if (++polls > kHandoffLimit) {
+                    if (lane == 0) {
+                        rq.set_flag(1);
+                        unsigned int *status = g_status_word;
+                        if (status) __hip_atomic_fetch_or(status, ENARF_STATUS_MARCH_WATCHDOG, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                        if (a.counters) atomicAdd(&a.counters[7], 1ull);
+                    }
+                    complete = false;
+                    break;
+                }
+                __builtin_amdgcn_s_sleep(1);
+            }
+            lds_acquire();
+            if (complete) ray_composite_stage<SPL>(a, sw, rid, rec.dmin, rec.dmax, S.mult_w, lane);
+        }
+        // What the barrier that used to stand after S3 ordered, and what orders it now:
+        //  * bins and skip flags (S4 and the fine tiles read them): rewritten by the next ray's S2, behind the next S1
+        //    barrier, which the S4 wave reaches only after S4 and every wave only after its fine tiles;
+        //  * fine arrays (S4 reads them): rewritten by the next fine pass, two barriers on, hence after S4;
+        //  * coarse arrays: rewritten by the next coarse tiles, which may now start while other waves are still in this
+        //    ray's fine tiles; their last reader was this ray's S2, complete before the S2 barrier every wave has passed;
+        //  * the ray's record and id: register copies since the top of the loop, so the pop that recycles the queue slot
+        //    (by the next ray's spare wave, which has passed this ray's S2 barrier) takes nothing away;
+        //  * change of image: the restage path above keeps its full barrier - a slow wave may still be in a fine tile on the
+        //    old image's pack - and the S4 wave joins it after S4;
+        //  * last ray (next_ray < 0): three waves leave the loop, wave 0 waits for all four counts and composites.
         cur = next_ray;
     }
     if (a.counters && lane == 0) {
@@ -917,7 +972,8 @@ int device_cus() {
 
 // Two march kernels run the same stage code (the tiles, S2 and S4 of enarf_tasks.h on a per-ray record in the slot layout of
 // enarf_march.h) and differ only in how they schedule it, so they produce the same bits:
-//   render_kernel   one workgroup (4 waves) marches one ray at a time, 3 workgroups per CU, three barriers per ray;
+//   render_kernel   one workgroup (4 waves) marches one ray at a time, 3 workgroups per CU, two barriers and a counted
+//                   hand-off (fine tiles -> compositing) per ray;
 //   march_kernel    one workgroup (12 waves) per CU, several rays in flight, 16-sample tiles claimed as tasks.
 // enarf_render_args.march picks one; ENARF_MARCH_AUTO picks by shape, from measurements on MI355X: the
 // task march wins where a pass has more tiles than a 4-wave workgroup has waves (Nc or Nf > 64: 0.31 vs 0.36 ms at 128^2,
@@ -952,6 +1008,27 @@ static int launch_task_march(const enarf_render_args &a, hipStream_t st, bool wi
     return host::check_launch("enarf_render_fwd");
 }
 
+// give render_kernel the device's status word (g_status_word): one copy per device, on the stream of its first launch and so
+// ahead of it. A capturing stream records the copy with the launch and leaves the device unmarked, so that the next eager
+// launch still makes it.
+static int publish_status_word(hipStream_t st) {
+    constexpr int kMaxDev = 64;
+    static unsigned int *word[kMaxDev] = {nullptr};       // the copy's source outlives the call
+    static bool done[kMaxDev] = {false};
+    static std::mutex mu;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return 0;      // no status word either (host::status_word)
+    std::lock_guard<std::mutex> lock(mu);
+    if (done[dev]) return 0;
+    word[dev] = host::status_word(true);
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
+    const hipError_t e = hipMemcpyToSymbolAsync(HIP_SYMBOL(g_status_word), &word[dev], sizeof(word[dev]), 0, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return host::fail((int)e, "enarf_render_fwd: hipMemcpyToSymbolAsync(status word) failed: %s", hipGetErrorString(e));
+    done[dev] = cap == hipStreamCaptureStatusNone;
+    return 0;
+}
+
 template <int MODE, int SPL>
 static int launch_render(const enarf_render_args &a, hipStream_t st, bool with_setup) {
     if (a.march == ENARF_MARCH_TASK || (a.march == ENARF_MARCH_AUTO && SPL == 2 && a.B == 1))
@@ -966,6 +1043,7 @@ static int launch_render(const enarf_render_args &a, hipStream_t st, bool with_s
     const size_t lds = (size_t)lds_total_floats<MODE>(a.P) * 4;
     if (with_setup)
         if (int rc = launch_ray_setup(a, st)) return rc;
+    if (int rc = publish_status_word(st)) return rc;
     hipLaunchKernelGGL((render_kernel<MODE, SPL>), dim3((unsigned)wgs), dim3(256), lds, st, a);
     return host::check_launch("enarf_render_fwd");
 }

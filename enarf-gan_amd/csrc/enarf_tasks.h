@@ -5,8 +5,8 @@
 //   S2      ray_sample_stage      coarse weights, smoothing, importance samples (bins_from_cdf of the uniforms that
 //                                 draw_sorted_uniforms drew), early-termination flags
 //   S4      ray_composite_stage   compositing and the ray's outputs
-// They differ only in the schedule: render_kernel (enarf_render.hip) marches one ray per 4-wave workgroup behind three
-// barriers; march_kernel, below, keeps several rays in flight. Same stages, same bits; enarf_render_args.march picks one.
+// They differ only in the schedule: render_kernel (enarf_render.hip) marches one ray per 4-wave workgroup behind two
+// barriers and a counted hand-off; march_kernel, below, keeps several rays in flight. Same stages, same bits; enarf_render_args.march picks one.
 //
 // One persistent workgroup of NW wavefronts per CU keeps R rays in flight, each in an LDS "slot". A ray's life is a chain
 //     pop -> C coarse tiles -> S2 (weights, importance samples) -> F fine tiles -> S4 (compositing, outputs) -> pop ...

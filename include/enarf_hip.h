@@ -64,7 +64,9 @@ const char *enarf_last_error(void);
  * status word could not be set up. The reference has no counterpart: its kernels cannot give up (kernel.cu:245-246). */
 #define ENARF_STATUS_MARCH_WATCHDOG 1u   /* enarf_render_fwd / _step_fwd with the task march (ENARF_MARCH_TASK, or AUTO for
                                             Nc / Nf > 64 at B == 1): a wave found no work for ~0.3 s although rays were in
-                                            flight and ended the launch; that launch's outputs are INCOMPLETE */
+                                            flight and ended the launch; with the ray march: the wave that composites a
+                                            ray waited that long for the ray's fine tiles and ended its workgroup's march;
+                                            that launch's outputs are INCOMPLETE */
 int enarf_device_status(unsigned int *flags, int clear);
 
 /* ---------------------------------------------------------------------------------------------
@@ -244,8 +246,9 @@ typedef struct {
                                              [0] valid (part,point) pairs sampled, [1] MLP tiles of 16 points run,
                                              [2] rays marched (rays that miss every cube included, dropped rays not),
                                              [3] gather rounds (wave-level), [4] fine tiles skipped by early_stop_eps,
-                                             [5], [6] unused by the product library, [7] != 0: the task march's
-                                             scheduler watchdog fired and the outputs are incomplete (never expected) */
+                                             [5], [6] unused by the product library, [7] != 0: a march watchdog
+                                             (ENARF_STATUS_MARCH_WATCHDOG) fired and the outputs are incomplete (never
+                                             expected) */
     void *workspace;                      /* device, >= enarf_render_workspace_bytes(B, n): two queue headers, per-ray
                                              records (depth range, candidate parts, direction) and the ray lists; one
                                              workspace must not be shared by launches that can overlap. */

@@ -9,11 +9,14 @@ is generated inside `enarf_query_fwd` (lattice mode, density only, one launch; o
 `rasterize_mesh` is `render_mesh_`'s hard-Phong image of such a mesh, rendered on the device (libenarf_raster.so);
 `render_mesh_` itself keeps pytorch3d. `vertex_colors` is the radiance field's colour at the vertices, `paint_mesh` the
 image of the mesh in those colours or in the colours of its part labels (rasterize_mesh, then the deferred shading of
-libenarf_paint.so); `export_obj` and `export_ply` carry the colours and labels out.
+libenarf_paint.so); `export_obj` and `export_ply` carry the colours and labels out. `extract_rigged_mesh` binds such a mesh
+to the model's parts (a `RiggedMesh`: extract_mesh plus one skin-weight launch of libenarf_skin.so), `skin_mesh` poses it by
+linear-blend skinning without a new extraction, and `export_glb` writes it as a skinned binary glTF.
 """
 from __future__ import annotations
 
-from typing import Dict
+import dataclasses
+from typing import Dict, Optional
 
 import torch
 
@@ -113,15 +116,10 @@ def point_part_labels(model, pose_to_camera: torch.Tensor, points: torch.Tensor,
     UNSCALED translation, as for density_volume. One launch; the tri-plane is the one the density sweep reads."""
     from ..NeRF.rendering import _parts_from_part_poses
     parts = _parts_from_part_poses(model, pose_to_camera, model_input["bone_length"])
-    tri = model_input.get("tri_plane_feature")
-    if tri is None:
-        tri = model.tri_plane if model.uses_warp else model.compute_tri_plane_feature(
-            model_input.get("z"), model_input["bone_length"], model_input.get("truncation_psi", 1))
-    if tri.shape[0] > 1 and tri.stride(0) == 0:       # an expanded constant tri-plane
-        tri = tri[:1]
+    tri = _mask_tri_plane(model, model_input)
     cs = model.coordinate_scale
     flags = model.kernel_flags()
-    return ops.part_labels(points.float() * cs if cs != 1 else points.float(), parts, model.canonical_pose, tri.detach(),
+    return ops.part_labels(points.float() * cs if cs != 1 else points.float(), parts, model.canonical_pose, tri,
                            clamp_mask=flags["clamp_mask"], uniform_part_weight=flags["uniform_part_weight"],
                            points_last=points_last, return_valid_bits=return_valid_bits)
 
@@ -164,6 +162,72 @@ def extract_mesh(model, pose_to_camera: torch.Tensor, center: torch.Tensor, voxe
     if return_colors:
         out += (vertex_colors(model, pose_to_camera, vertices, model_input),)
     return out
+
+
+@dataclasses.dataclass
+class RiggedMesh:
+    """A mesh bound to the parts of the model it was extracted from: vertices (V, 3) fp32 in camera units in the rest
+    pose, triangles (T, 3) int64, joints (V, K) int32 (-1: unused slot) and weights (V, K) fp32 by descending weight,
+    kept_mass (V,) fp32 (the share of the part-probability mass the K kept parts carry; 0: no part contains the vertex, it
+    follows the nearest), rest_pose (1, P, 4, 4) the rest part frames with UNSCALED translation, rest_bone_length
+    (1, P, 1), and optionally colors (V, 3) fp32 in [0, 1] and labels (V,) int32."""
+    vertices: torch.Tensor
+    triangles: torch.Tensor
+    joints: torch.Tensor
+    weights: torch.Tensor
+    kept_mass: torch.Tensor
+    rest_pose: torch.Tensor
+    rest_bone_length: torch.Tensor
+    colors: Optional[torch.Tensor] = None
+    labels: Optional[torch.Tensor] = None
+
+
+def _mask_tri_plane(model, model_input: Dict) -> torch.Tensor:
+    """the tri-plane whose part-probability planes point_part_labels reads"""
+    tri = model_input.get("tri_plane_feature")
+    if tri is None:
+        tri = model.tri_plane if model.uses_warp else model.compute_tri_plane_feature(
+            model_input.get("z"), model_input["bone_length"], model_input.get("truncation_psi", 1))
+    if tri.shape[0] > 1 and tri.stride(0) == 0:       # an expanded constant tri-plane
+        tri = tri[:1]
+    return tri.detach()
+
+
+@torch.no_grad()
+def extract_rigged_mesh(model, pose_to_camera: torch.Tensor, center: torch.Tensor, voxel_size: float = 0.003,
+                        mesh_th: float = 15, model_input: Dict = {}, max_influences: int = 4, return_colors: bool = False,
+                        return_part_labels: bool = False) -> RiggedMesh:
+    """extract_mesh in the pose pose_to_camera (1, P, 4, 4) - the rest pose of the rig - plus one ops.skin_weights launch
+    over the vertex array: every vertex bound to the max_influences (4 or 8) parts of the largest part probability among
+    the parts whose cube contains it. `return_colors` and `return_part_labels` fill the record's colors and labels as
+    extract_mesh returns them. The mesh is posed by skin_mesh and written out by export_glb."""
+    from ..NeRF.rendering import _parts_from_part_poses
+    got = extract_mesh(model, pose_to_camera, center, voxel_size, mesh_th, model_input, return_part_labels, return_colors)
+    vertices, triangles, extra = got[0], got[1], list(got[2:])
+    labels = extra.pop(0) if return_part_labels else None
+    colors = extra.pop(0) if return_colors else None
+    bone_length = model_input["bone_length"]
+    parts = _parts_from_part_poses(model, pose_to_camera, bone_length)
+    flags = model.kernel_flags()
+    joints, weights, kept = ops.skin_weights(vertices, parts, model.canonical_pose, _mask_tri_plane(model, model_input),
+                                             max_influences=max_influences, clamp_mask=flags["clamp_mask"],
+                                             uniform_part_weight=flags["uniform_part_weight"],
+                                             coordinate_scale=float(model.coordinate_scale))
+    return RiggedMesh(vertices, triangles, joints, weights, kept, pose_to_camera.detach().float().clone(),
+                      bone_length.detach().float().reshape(1, -1, 1).clone(), colors, labels)
+
+
+@torch.no_grad()
+def skin_mesh(model, rig: RiggedMesh, pose_to_camera: torch.Tensor, bone_length: torch.Tensor, out=None) -> torch.Tensor:
+    """The rigged mesh in F poses: (F, V, 3) fp32 vertices in camera units, one ops.skin_pose launch, no new extraction.
+    pose_to_camera (F, P, 4, 4) part frames with UNSCALED translation, as for point_part_labels; bone_length (F, P, 1) or
+    (1, P, 1) part bone lengths (a bone longer than in the rest pose stretches its part). `out` as in ops.skin_pose."""
+    from ..NeRF.rendering import _parts_from_part_poses
+    F, P = pose_to_camera.shape[:2]
+    rest = _parts_from_part_poses(model, rig.rest_pose, rig.rest_bone_length)
+    parts = _parts_from_part_poses(model, pose_to_camera.float(), bone_length.float().reshape(-1, P, 1).expand(F, -1, -1))
+    return ops.skin_pose(rig.vertices, rig.joints, rig.weights, rest, parts, coordinate_scale=float(model.coordinate_scale),
+                         out=out)
 
 
 def _host(a, dtype=None):
@@ -229,6 +293,101 @@ def export_ply(vertices, triangles, path: str, colors=None, labels=None) -> None
         fh.write(("\n".join(header) + "\n").encode("ascii"))
         fh.write(vert.tobytes())
         fh.write(face.tobytes())
+
+
+def _quaternion(R):
+    """(P, 3, 3) rotation matrices (float64) -> (P, 4) unit quaternions (x, y, z, w), w >= 0"""
+    import numpy as np
+    q = np.empty((len(R), 4))
+    for i, m in enumerate(R):
+        tr = m[0, 0] + m[1, 1] + m[2, 2]
+        if tr > 0:
+            s = 2.0 * np.sqrt(1.0 + tr)
+            q[i] = [(m[2, 1] - m[1, 2]) / s, (m[0, 2] - m[2, 0]) / s, (m[1, 0] - m[0, 1]) / s, 0.25 * s]
+        else:
+            a = int(np.argmax([m[0, 0], m[1, 1], m[2, 2]]))
+            b, c = (a + 1) % 3, (a + 2) % 3
+            s = 2.0 * np.sqrt(max(1.0 + m[a, a] - m[b, b] - m[c, c], 1e-300))
+            q[i, a], q[i, b], q[i, c], q[i, 3] = 0.25 * s, (m[b, a] + m[a, b]) / s, (m[c, a] + m[a, c]) / s, (m[c, b] - m[b, c]) / s
+        q[i] /= np.linalg.norm(q[i])
+        if q[i, 3] < 0:
+            q[i] = -q[i]
+    return q
+
+
+def export_glb(rig: RiggedMesh, path: str) -> None:
+    """The rigged mesh as binary glTF 2.0 (standard library and numpy only): one mesh primitive with POSITION, optional
+    COLOR_0 (float RGB), JOINTS_0 / WEIGHTS_0 and, at 8 influences, JOINTS_1 / WEIGHTS_1 (joints as unsigned bytes, an
+    unused slot as joint 0 with weight 0), 32-bit indices; a flat skeleton of P joint nodes under one identity root, node
+    k carrying the rest frame of part k as translation and rotation (its rest bone length in `extras`), and
+    inverseBindMatrices = the inverses of the rest frames. A viewer that sets node k to (t_k, R_k, uniform scale
+    bone_length_k / rest bone_length_k) of another pose reproduces skin_mesh. No animation clips."""
+    import json
+    import struct
+    import numpy as np
+    v = _host(rig.vertices, np.float32).reshape(-1, 3)
+    f = _host(rig.triangles, np.int64).reshape(-1, 3)
+    joints, weights = _host(rig.joints, np.int64), _host(rig.weights, np.float32)
+    frames = _host(rig.rest_pose, np.float64).reshape(-1, 4, 4)
+    bone = _host(rig.rest_bone_length, np.float64).reshape(-1)
+    P, K = len(frames), joints.shape[1]
+    if joints.shape != (len(v), K) or weights.shape != joints.shape or K not in (4, 8):
+        raise ValueError(f"export_glb takes ({len(v)}, 4 or 8) joints and weights, got {joints.shape} and {weights.shape}")
+    if P > 256 or (joints.size and joints.max() >= P):
+        raise ValueError(f"export_glb: joints up to {int(joints.max())} with {P} parts (joints are unsigned bytes)")
+    if len(f) and (f.min() < 0 or f.max() >= len(v)):
+        raise ValueError("export_glb: a triangle names a vertex the mesh does not have")
+    weights = np.where(joints >= 0, weights, np.float32(0)).astype(np.float32)
+    joints = np.where(joints >= 0, joints, 0).astype(np.uint8)
+    R, t = frames[:, :3, :3], frames[:, :3, 3]
+    inverse = np.tile(np.eye(4), (P, 1, 1))
+    inverse[:, :3, :3] = R.transpose(0, 2, 1)
+    inverse[:, :3, 3] = -np.einsum("pji,pj->pi", R, t)
+    chunks, views, accessors = [], [], []
+
+    def add(array, kind, component, target=None, bounds=False):
+        data = np.ascontiguousarray(array).tobytes()
+        offset = sum(len(c) for c in chunks)
+        chunks.append(data + b"\0" * (-len(data) % 4))
+        view = {"buffer": 0, "byteOffset": offset, "byteLength": len(data)}
+        if target is not None:
+            view["target"] = target
+        views.append(view)
+        acc = {"bufferView": len(views) - 1, "componentType": component, "count": len(array), "type": kind}
+        if bounds:
+            acc["min"], acc["max"] = [float(x) for x in array.min(axis=0)], [float(x) for x in array.max(axis=0)]
+        accessors.append(acc)
+        return len(accessors) - 1
+
+    FLOAT, UBYTE, UINT, ARRAY, ELEMENT = 5126, 5121, 5125, 34962, 34963
+    attributes = {"POSITION": add(v, "VEC3", FLOAT, ARRAY, bounds=len(v) > 0)}
+    if rig.colors is not None:
+        c = np.clip(np.nan_to_num(_host(rig.colors, np.float32).reshape(-1, 3), nan=0.0), 0, 1)
+        if c.shape != v.shape:
+            raise ValueError(f"export_glb takes ({len(v)}, 3) colors, got {c.shape}")
+        attributes["COLOR_0"] = add(c, "VEC3", FLOAT, ARRAY)
+    for s in range(K // 4):
+        attributes[f"JOINTS_{s}"] = add(joints[:, 4 * s:4 * s + 4], "VEC4", UBYTE, ARRAY)
+        attributes[f"WEIGHTS_{s}"] = add(weights[:, 4 * s:4 * s + 4], "VEC4", FLOAT, ARRAY)
+    indices = add(f.astype(np.uint32).reshape(-1), "SCALAR", UINT, ELEMENT)
+    ibm = add(inverse.transpose(0, 2, 1).astype(np.float32).reshape(P, 16), "MAT4", FLOAT)      # column-major
+    quat = _quaternion(R)
+    nodes = [{"name": f"part_{k}", "translation": [float(np.float32(x)) for x in t[k]],
+              "rotation": [float(np.float32(x)) for x in quat[k]], "extras": {"bone_length": float(bone[k])}} for k in range(P)]
+    nodes.append({"name": "skeleton", "children": list(range(P))})
+    nodes.append({"name": "mesh", "mesh": 0, "skin": 0})
+    doc = {"asset": {"version": "2.0", "generator": "enarf_gan_amd export_glb"}, "scene": 0,
+           "scenes": [{"nodes": [P, P + 1]}], "nodes": nodes,
+           "meshes": [{"primitives": [{"attributes": attributes, "indices": indices, "mode": 4}]}],
+           "skins": [{"joints": list(range(P)), "inverseBindMatrices": ibm, "skeleton": P}],
+           "buffers": [{"byteLength": sum(len(c) for c in chunks)}], "bufferViews": views, "accessors": accessors}
+    text = json.dumps(doc, separators=(",", ":")).encode("utf-8")
+    text += b" " * (-len(text) % 4)
+    binary = b"".join(chunks)
+    with open(path, "wb") as fh:
+        fh.write(struct.pack("<4sII", b"glTF", 2, 12 + 8 + len(text) + 8 + len(binary)))
+        fh.write(struct.pack("<I4s", len(text), b"JSON") + text)
+        fh.write(struct.pack("<I4s", len(binary), b"BIN\0") + binary)
 
 
 def export_point_cloud(points, flags, path: str, colors=None, normals=None) -> None:

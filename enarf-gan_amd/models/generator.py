@@ -203,6 +203,58 @@ class TriNARFGenerator(_RendererShell):
             frames[i] = ops.shade_fragments(f.pix_to_face, f.bary, f.normals, turned, triangles, lit=lit, **how).image
         return frames
 
+    def extract_rigged_mesh(self, pose_to_camera, z, bone_length, voxel_size=0.003, mesh_th=15, truncation_psi=0.4,
+                            max_influences=4, return_colors=False, return_part_labels=False):
+        """extract_mesh in the rest pose pose_to_camera, bound to the model's parts: a RiggedMesh (mesh_rendering) with
+        joints and weights (V, max_influences = 4 or 8) from one launch of the HIP skin-weight kernel, ready for
+        render_mesh_animation, mesh_rendering.skin_mesh and mesh_rendering.export_glb; one sample, as extract_mesh."""
+        z_nerf, z_render, _ = self._latent_parts(z)
+        return self.nerf.extract_rigged_mesh(pose_to_camera, z_nerf, z_render, bone_length, voxel_size, mesh_th,
+                                             truncation_psi, max_influences, return_colors, return_part_labels)
+
+    def render_mesh_animation(self, rig, key_poses, bone_length, intrinsics, num=100, loop=True, orbit=None, color="field",
+                              lit=True, render_size=512, frames_per_batch=8):
+        """The rigged mesh in motion, without a new extraction: (frames (num, R, R, 3) uint8, poses (num, J, 4, 4) in
+        key_poses' dtype), device tensors, with no host synchronisation inside. One interpolate_pose launch; the frames
+        posed frames_per_batch at a time by one skin_pose launch (linear-blend skinning of `rig`, the RiggedMesh of
+        extract_rigged_mesh); every frame one rasterize_mesh and one shade_fragments, as render_mesh_turntable.
+        color="field" draws rig.colors, "parts" the palette colours of rig.labels, None the white mesh; bone_length
+        (1, J - 1, 1) are the bone lengths of the animation (a bone longer than the rig's stretches its part). The bytes
+        do not depend on frames_per_batch."""
+        from .. import ops
+        from ..libraries.NARF.mesh_rendering import rasterize_mesh, skin_mesh
+        from ..libraries.NeRF.rendering import semantic_palette
+        if color not in ("field", "parts", None):
+            raise ValueError(f"color is 'field', 'parts' or None (the white mesh), got {color!r}")
+        if color == "field" and rig.colors is None or color == "parts" and rig.labels is None:
+            raise ValueError(f"color={color!r} takes a rig extracted with "
+                             f"{'return_colors' if color == 'field' else 'return_part_labels'}=True")
+        if bone_length.shape[0] != 1:
+            raise AssertionError("render_mesh_animation takes one identity: bone_length of batch 1")
+        per = int(frames_per_batch)
+        if per < 1:
+            raise ValueError(f"render_mesh_animation: frames_per_batch {frames_per_batch} < 1")
+        nerf, R = self.nerf, int(render_size)
+        with torch.no_grad():
+            poses, poses32 = ops.interpolate_pose(key_poses, nerf.parent_id, num, loop, orbit, return_f32=True)
+            dev, n_frames, V = poses.device, poses.shape[0], rig.vertices.shape[0]
+            how = {}
+            if color == "field":
+                how = dict(vertex_colors=rig.colors)
+            elif color == "parts":
+                how = dict(vertex_labels=rig.labels, palette=(semantic_palette(nerf.num_bone, dev) + 1) / 2)
+            frames = torch.empty((n_frames, R, R, 3), dtype=torch.uint8, device=dev)
+            posed = torch.empty((min(per, n_frames), V, 3), dtype=torch.float32, device=dev)
+            for a in range(0, n_frames, per):
+                b = min(a + per, n_frames)
+                pose_parts, bl = nerf.transform_pose(poses32[a:b], bone_length.float().expand(b - a, -1, -1))
+                skin_mesh(nerf, rig, pose_parts, bl, out=posed[:b - a])
+                for i in range(a, b):
+                    f = rasterize_mesh(posed[i - a], rig.triangles, intrinsics, self.size, R)
+                    frames[i] = (ops.shade_fragments(f.pix_to_face, f.bary, f.normals, posed[i - a], rig.triangles, lit=lit,
+                                                     **how).image if how else f.image)
+        return frames, poses
+
     def render_part_animation(self, key_poses, bone_length, intrinsics, z, num=100, loop=True, orbit=None,
                               truncation_psi=0.4, frames_per_batch=8, background=1.0):
         """render_animation of the part segmentation: (frames (num, S, S, 3) uint8 in the colours of semantic_palette over

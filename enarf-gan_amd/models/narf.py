@@ -366,6 +366,16 @@ class TriPlaneNARF(nn.Module):
         center, pose_parts, model_input = self._mesh_inputs(pose_to_camera, z, z_rend, bone_length, truncation_psi)
         return extract_mesh(self, pose_parts, center, voxel_size, mesh_th, model_input, return_part_labels, return_colors)
 
+    def extract_rigged_mesh(self, pose_to_camera, z, z_rend, bone_length, voxel_size=0.003, mesh_th=15, truncation_psi=0.4,
+                            max_influences=4, return_colors=False, return_part_labels=False):
+        """extract_mesh in the rest pose pose_to_camera (1, J, 4, 4), bound to the parts: the RiggedMesh of
+        mesh_rendering.extract_rigged_mesh (vertices, triangles, joints and weights (V, max_influences), kept_mass, the
+        rest part frames and bone lengths, optional colours and labels). One skin-weight launch more than extract_mesh."""
+        from ..libraries.NARF.mesh_rendering import extract_rigged_mesh
+        center, pose_parts, model_input = self._mesh_inputs(pose_to_camera, z, z_rend, bone_length, truncation_psi)
+        return extract_rigged_mesh(self, pose_parts, center, voxel_size, mesh_th, model_input, max_influences, return_colors,
+                                   return_part_labels)
+
     def part_labels(self, points, pose_to_camera, z, bone_length, truncation_psi=1, points_last=False,
                     return_valid_bits=False):
         """The part that owns each point: (label (B, M) int32, top (B, M), second (B, M)[, valid_bits]) of

@@ -944,6 +944,36 @@ def shade_fragments(pix_to_face: torch.Tensor, bary: torch.Tensor, normals: torc
                                       lit, background, neutral)
 
 
+# ------------------------------------------------------------------------------------------------- rigged meshes
+def skin_weights(vertices: torch.Tensor, parts_rest: torch.Tensor, canonical_pose: torch.Tensor, tri_plane: torch.Tensor, *,
+                 max_influences: int = 4, clamp_mask: bool = False, uniform_part_weight: bool = False,
+                 coordinate_scale: float = 1.0, return_valid_bits: bool = False):
+    """The skin weights of mesh vertices, in one launch of libenarf_skin.so: (joints (V, K) int32, weights (V, K) fp32,
+    kept_mass (V,) fp32[, valid_bits (V,) int32]), K = max_influences (4 or 8). A vertex is bound to the K parts of the
+    largest tri-plane part probability among the parts whose cube contains it in the rest pose (part_labels' validity and
+    weights; the lower index first among equals), by descending weight, the weights normalised to sum 1; unused slots
+    hold joint -1 and weight 0. kept_mass is the share of the whole probability mass the kept parts carry (1 when at most
+    K parts contain the vertex). A vertex no cube contains follows the part whose cube is nearest (joint slot 0, weight 1,
+    kept_mass 0). vertices (V, 3) fp32 in camera units (a (3, V).t() view is read in place), multiplied by
+    coordinate_scale in the kernel; parts_rest (1, P, 16) from prepare, tri_plane the (1, 96 + 3P, H, W) tri-plane.
+    Nothing synchronises; V = 0 returns empty tensors without a launch."""
+    from . import _skin_lib
+    return _skin_lib.skin_weights(vertices, parts_rest, canonical_pose, tri_plane, max_influences, clamp_mask,
+                                  uniform_part_weight, coordinate_scale, return_valid_bits)
+
+
+def skin_pose(vertices: torch.Tensor, joints: torch.Tensor, weights: torch.Tensor, parts_rest: torch.Tensor,
+              parts: torch.Tensor, *, coordinate_scale: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The mesh in F poses, in one launch of libenarf_skin.so: (F, V, 3) fp32, frame f = sum_j weights[:, j] M_j^f v with
+    M_k^f = rho_k R_k^f R_k^rest^T (v - t_k^rest) + t_k^f and rho_k the bone-length ratio of frame f over the rest pose:
+    linear-blend skinning with one uniform scale a bone. vertices (V, 3) fp32 in camera units, joints and weights (V, 4 or
+    8) from skin_weights, parts_rest (1, P, 16) and parts (F, P, 16) from prepare (their translations are divided by
+    coordinate_scale). `out` writes into a given (F, V, 3) tensor or slice whose frames are contiguous. Computed in fp64
+    from the fp32 inputs and rounded once, bit-identical from run to run, nothing synchronises."""
+    from . import _skin_lib
+    return _skin_lib.skin_pose(vertices, joints, weights, parts_rest, parts, coordinate_scale, out)
+
+
 # ------------------------------------------------------------------------------------------------- geometry buffers
 from ._geom_lib import DepthError, GeometryBuffers  # noqa: E402,F401  (the running depth error; geometry_buffers' result)
 

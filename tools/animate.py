@@ -9,6 +9,8 @@ compose_frames launch per chunk) and a single copy of the finished uint8 frames 
   python tools/animate.py ... --parts --out parts/                 # the part segmentation in motion (render_part_animation)
   python tools/animate.py ... --mesh-turntable field --out turn/   # the coloured mesh of the first key on a turntable
   python tools/animate.py ... --geometry normal --out shape/       # the march's own geometry in motion (render_geometry_animation)
+  python tools/animate.py ... --skinned-mesh field --out skin/     # the first key's mesh, rigged once, posed per frame
+  python tools/animate.py ... --skinned-mesh parts --export-glb avatar.glb --out skin/   # ... and the rig as binary glTF
 
 The key poses, the camera and the bone lengths are entries of a sample_data.pickle (formats.read_sample_data; the
 camera and bone lengths of the first key); `--canonical` is the canonical pose (24, 4, 4) the model was trained with
@@ -19,7 +21,11 @@ are reported. `num` must be a multiple of the number of keys (with --no-loop: of
 extracts the mesh of the first key once (HIP marching cubes), in the radiance field's colours or the part colours, and
 turns it through `--num` angles of one turn (render_mesh_turntable: HIP rasteriser and deferred shading per frame).
 `--geometry normal|lit|depth` draws the shape the march itself carries - the normal map, a lit white surface, or the
-inverse depth between `--depth-range` - from the disparity of each frame (ops.geometry_buffers, no mesh extracted)."""
+inverse depth between `--depth-range` - from the disparity of each frame (ops.geometry_buffers, no mesh extracted).
+`--skinned-mesh field|parts|white` extracts the mesh of the first key once, binds it to the model's parts
+(extract_rigged_mesh: `--influences` 4 or 8 a vertex) and moves it through the key poses by linear-blend skinning
+(render_mesh_animation: one skin_pose launch a chunk, HIP rasteriser and deferred shading per frame); `--export-glb PATH`
+writes that rig as a skinned binary glTF (mesh_rendering.export_glb), with or without --skinned-mesh."""
 import argparse
 import math
 import os
@@ -53,6 +59,10 @@ def main():
     ap.add_argument("--depth-range", default="1.0,5.0", help="--geometry depth: near,far in the poses' units")
     ap.add_argument("--mesh-turntable", choices=["field", "parts"], default=None,
                     help="a turntable of the first key's coloured mesh in place of the march")
+    ap.add_argument("--skinned-mesh", choices=["field", "parts", "white"], default=None,
+                    help="the first key's mesh, rigged once and posed per frame, in place of the march")
+    ap.add_argument("--influences", type=int, choices=[4, 8], default=4, help="skinned mesh: parts a vertex is bound to")
+    ap.add_argument("--export-glb", default=None, help="write the rigged mesh of the first key as binary glTF to this path")
     ap.add_argument("--voxel-size", type=float, default=0.003, help="mesh turntable: the density sweep's voxel")
     ap.add_argument("--mesh-th", type=float, default=15.0, help="mesh turntable: the density threshold")
     ap.add_argument("--unlit", action="store_true", help="mesh turntable: the colour itself, without the Phong terms")
@@ -86,7 +96,22 @@ def main():
     orbit = None
     if args.orbit_turns:
         orbit = torch.arange(args.num, dtype=torch.float64, device=dev) * (2 * math.pi * args.orbit_turns / args.num)
-    if args.mesh_turntable:
+    rig = None
+    if args.skinned_mesh or args.export_glb:
+        rig = gen.extract_rigged_mesh(key_poses[:1].float(), z, bone_length, voxel_size=args.voxel_size, mesh_th=args.mesh_th,
+                                      truncation_psi=args.truncation_psi, max_influences=args.influences,
+                                      return_colors=True, return_part_labels=True)
+        if args.export_glb:
+            from enarf_gan_amd.libraries.NARF.mesh_rendering import export_glb
+            export_glb(rig, args.export_glb)
+            print(f"{args.export_glb}: {len(rig.vertices)} vertices, {len(rig.triangles)} triangles, "
+                  f"{rig.joints.shape[1]} influences", file=sys.stderr)
+    if args.skinned_mesh:
+        frames, _ = gen.render_mesh_animation(rig, key_poses, bone_length, intrinsics, num=args.num, loop=not args.no_loop,
+                                              orbit=orbit, color=None if args.skinned_mesh == "white" else args.skinned_mesh,
+                                              lit=not args.unlit, render_size=args.render_size,
+                                              frames_per_batch=args.frames_per_batch)
+    elif args.mesh_turntable:
         angles = torch.arange(args.num, dtype=torch.float32, device=dev) * (2 * math.pi / args.num)
         frames = gen.render_mesh_turntable(key_poses[:1].float(), intrinsics, z, bone_length, angles,
                                            voxel_size=args.voxel_size, mesh_th=args.mesh_th,

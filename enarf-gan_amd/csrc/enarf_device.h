@@ -1,4 +1,5 @@
-// enarf_device.h - shared device code of libenarf_hip.so (gfx950 / CDNA4 only, wave64).
+// enarf_device.h - device code shared by the libraries (gfx950 / CDNA4 only, wave64): inline functions only, no kernel,
+// since every library's kernel inventory is closed.
 //
 // Conventions
 //   * "exact" functions spell every 3x3 product as ((a0*b0 + a1*b1) + a2*b2) with FMA contraction
@@ -108,6 +109,16 @@ __device__ __forceinline__ float wave_scan_incl(float v, int lane) {
 }
 __device__ __forceinline__ float wave_sum(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, wave_scan_incl(v, 0)), 63));
+}
+
+// sum over the workgroup's 256 threads, returned to every thread; `red` holds 4 doubles
+__device__ __forceinline__ double block_sum(double v, double *red) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    __syncthreads();                                    // the previous call's readers are done with `red`
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
 }
 
 // ---- "wave vectors": SPL values per lane = SPL * 64 elements along a ray, element e = 64 s + lane --------------------
@@ -406,5 +417,11 @@ __device__ __forceinline__ void philox4x32(uint32_t c0, uint32_t c1, uint32_t c2
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 __device__ __forceinline__ float u32_to_unit(uint32_t x) { return (float)(x >> 8) * (1.0f / 16777216.0f); }   // [0,1)
+
+// ---- 8-bit image level: floor(255 clamp(x, 0, 1)); a NaN fails x > 0 and gives 0 ---------------------
+__device__ __forceinline__ uint8_t level(double x) {
+    if (!(x > 0.0)) return 0;
+    return (uint8_t)(int)floor(255.0 * (x < 1.0 ? x : 1.0));
+}
 
 }  // namespace enarf

@@ -12,6 +12,7 @@
 // Everything is fp64 from the fp32 inputs with FMA contraction off, as in enarf_raster.hip and enarf_paint.hip, so the
 // float64 restatement of the contract (tests/geom_reference.py) is matched to the rounding of the stored fp32.
 #include "enarf_geom.h"
+#include "enarf_device.h"
 #include "enarf_host.h"
 
 #include <hip/hip_runtime.h>
@@ -20,18 +21,14 @@
 
 namespace {
 
+using enarf::level;
+
 constexpr int kTile = 16;
 constexpr int kBlock = 256;
 constexpr int kMaxSize = ENARF_GEOM_MAX_SIZE;
 constexpr long long kMaxCount = 1LL << 31;
 constexpr int kWords = ENARF_GEOM_STATE_WORDS;
 constexpr int kPerLane = 8;              // pixels a lane takes before another workgroup is added
-
-// floor(255 clamp(x, 0, 1)); a NaN fails x > 0 and gives 0
-__device__ __forceinline__ uint8_t level(double x) {
-    if (!(x > 0.0)) return 0;
-    return (uint8_t)(int)floor(255.0 * (x < 1.0 ? x : 1.0));
-}
 
 struct Sample {
     bool valid;

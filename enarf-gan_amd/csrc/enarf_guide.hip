@@ -16,6 +16,7 @@
 // the chunk's share of tied values precede it in the chunk (a 256-wide scan per row, only in the one chunk whose share
 // is neither nothing nor everything).
 #include "enarf_guide.h"
+#include "enarf_device.h"
 #include "enarf_host.h"
 
 #include <hip/hip_runtime.h>
@@ -23,6 +24,8 @@
 #include <stdint.h>
 
 namespace {
+
+using enarf::block_sum;
 
 constexpr int kBlock = 256;
 constexpr int kMaxBlocks = ENARF_GUIDE_MAX_BLOCKS;
@@ -85,16 +88,6 @@ __device__ __forceinline__ bool on_bone(const Args &a, long long i) {
             nan |= v != v;
         }
     return any && !nan;
-}
-
-// sum over the workgroup's 256 threads, returned to every thread; `red` holds 4 doubles
-__device__ __forceinline__ double block_sum(double v, double *red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    __syncthreads();                                    // the previous call's readers are done with `red`
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
 }
 
 // inclusive prefix sum over the workgroup's 256 threads in thread order; `tot` holds 4 counters

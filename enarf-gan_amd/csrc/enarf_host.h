@@ -1,4 +1,5 @@
-// enarf_host.h - host-side error plumbing of the C ABI (thread-local last-error string).
+// enarf_host.h - host-side plumbing of the C ABI: the thread-local last-error string, argument checks and workspace
+// layout helpers that more than one library uses. Included after a public header (they define ENARF_ERR_ARG).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdarg>
@@ -27,6 +28,18 @@ inline int check_launch(const char *who) {
     if (e != hipSuccess) return fail((int)e, "%s: launch failed: %s", who, hipGetErrorString(e));
     return 0;
 }
+
+// the arguments of a kernel that walks the parts (enarf_parts.h): P parts in the bit mask, 3 P part-probability planes of H x W
+// whose byte offsets stay below 2^32. 0, or the failure to return
+inline int check_part_planes(const char *who, int P, int max_parts, int H, int W) {
+    if (P < 1 || P > max_parts) return fail(ENARF_ERR_ARG, "%s: %d parts outside [1, %d]", who, P, max_parts);
+    if (H < 2 || W < 2 || 3LL * P * H * W >= (1LL << 30))
+        return fail(ENARF_ERR_ARG, "%s: planes %d x %d with %d parts: H, W >= 2 and 3 P H W < 2^30 floats", who, H, W, P);
+    return 0;
+}
+
+// sections of a device workspace start on 256-byte boundaries
+inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
 // Sticky status word of a device: 64 bytes of pinned host memory the device can write (allocated on first use, one per
 // device, never freed). A kernel that has to give up ORs a bit into it (ENARF_STATUS_*); enarf_device_status reads it

@@ -31,12 +31,7 @@ __device__ __forceinline__ void stage_common(float *lds, QueryCtx &S, float *&sc
     f32x4 *dst4 = reinterpret_cast<f32x4 *>(l_mlp);
     for (int i = tid; i < lds_mlp_floats<MODE>() / 4; i += nthreads) dst4[i] = src4[i];
     for (int i = tid; i < 144; i += nthreads) l_bias[i] = pf[PK_B1 + i];
-    for (int i = tid; i < P * kPartStride; i += nthreads)
-        l_parts[(i / kPartStride) * kLdsPartStride + (i % kPartStride)] = parts_b[i];
-    for (int i = tid; i < P * 12; i += nthreads) {   // (P,4,4) -> Rc row-major 9 + tc 3
-        const int k = i / 12, e = i % 12;
-        l_canon[i] = (e < 9) ? canon_pose[k * 16 + (e / 3) * 4 + (e % 3)] : canon_pose[k * 16 + (e - 9) * 4 + 3];
-    }
+    stage_frames(l_parts, l_canon, parts_b, canon_pose, P, tid, nthreads);
     S.mlp = l_mlp;
     S.mlp_h = reinterpret_cast<const short *>(l_mlp);
     S.bias = l_bias;

@@ -22,6 +22,8 @@
 
 namespace {
 
+using enarf::host::align256;
+
 constexpr int kWave = 64;
 constexpr int kWaves = 4;                         // waves per block
 constexpr int kRowsPerWave = 4;
@@ -32,8 +34,6 @@ struct Layout {
     long long rows, tiles;
     size_t vcnt, tcnt, tsum_v, tsum_t, tot, bytes;
 };
-
-inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
 inline Layout layout(int X, int Y) {
     Layout l;

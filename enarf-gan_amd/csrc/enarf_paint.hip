@@ -10,6 +10,7 @@
 // Everything is fp64 from the fp32 inputs with FMA contraction off, as in enarf_raster.hip, so the float64 restatement
 // of the contract (tests/paint_reference.py) is matched to the rounding of the stored fp32.
 #include "enarf_paint.h"
+#include "enarf_device.h"
 #include "enarf_host.h"
 
 #include <hip/hip_runtime.h>
@@ -18,15 +19,11 @@
 
 namespace {
 
+using enarf::level;
+
 constexpr int kBlock = 256;
 constexpr int kMaxR = ENARF_PAINT_MAX_SIZE;
 constexpr long long kMaxCount = 1LL << 31;
-
-// floor(255 clamp(x, 0, 1)); a NaN fails x > 0 and gives 0
-__device__ __forceinline__ uint8_t level(double x) {
-    if (!(x > 0.0)) return 0;
-    return (uint8_t)(int)floor(255.0 * (x < 1.0 ? x : 1.0));
-}
 
 // the corner of the largest stored b', compared as fp32: a later corner wins only when strictly larger
 __device__ __forceinline__ int top_corner(float b0, float b1, float b2) {

@@ -18,6 +18,7 @@
 // right, partials by strided lanes in index order and the same tree. Nothing depends on scheduling, so every output
 // is a function of the inputs alone.
 #include "enarf_photo.h"
+#include "enarf_device.h"
 #include "enarf_host.h"
 
 #include <hip/hip_runtime.h>
@@ -25,6 +26,8 @@
 #include <stdint.h>
 
 namespace {
+
+using enarf::block_sum;
 
 constexpr int kBlock = 256;
 constexpr int kTile = ENARF_PHOTO_TILE;
@@ -34,16 +37,6 @@ constexpr int kStage = kTile + 2 * kHalo;               // 22 rows / columns sta
 constexpr int kStagePitch = kStage + 1;
 constexpr int kChunk = 32;                              // images per metrics launch (their rectangles ride in the arguments)
 static_assert(kTile * kTile == kBlock, "one thread per tile pixel");
-
-// sum over the workgroup's 256 threads, returned to every thread; `red` holds 4 doubles
-__device__ __forceinline__ double block_sum(double v, double *red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    __syncthreads();                                    // the previous call's readers are done with `red`
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
 
 // ------------------------------------------------------------------------------------------------------- loss
 struct LossArgs {

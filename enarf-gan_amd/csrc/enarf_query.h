@@ -9,6 +9,7 @@
 //                 8g..8g+7), and hold exactly the B-operand fragments the MFMA MLP needs.
 #pragma once
 #include "enarf_device.h"
+#include "enarf_parts.h"
 
 namespace enarf {
 
@@ -529,21 +530,8 @@ __device__ __forceinline__ Taps quad_bcast_taps(const Taps &t) {
     return r;
 }
 
-// part frames / canonical frames in LDS: strides chosen so that 16 different parts read in one wave
-// instruction spread over the banks (16-float stride would put parts k and k+2 on the same banks)
-constexpr int kLdsPartStride = 20;   // 16 used
-constexpr int kLdsCanonStride = 12;
-
 __device__ __forceinline__ void load_frames(const QueryCtx &S, int k, float F[13], float Cn[12]) {
-    const f32x4 *pf = reinterpret_cast<const f32x4 *>(S.parts + k * kLdsPartStride);
-    const f32x4 *pc = reinterpret_cast<const f32x4 *>(S.canon + k * kLdsCanonStride);
-    const f32x4 f0 = pf[0], f1 = pf[1], f2 = pf[2], f3 = pf[3];
-    const f32x4 c0 = pc[0], c1 = pc[1], c2 = pc[2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { F[i] = f0[i]; F[4 + i] = f1[i]; F[8 + i] = f2[i]; }
-    F[12] = f3[0];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { Cn[i] = c0[i]; Cn[4 + i] = c1[i]; Cn[8 + i] = c2[i]; }
+    load_frames(S.parts, S.canon, k, F, Cn);
 }
 
 // ---- the query on one 16-point tile ---------------------------------------------------------------------------
@@ -570,9 +558,8 @@ __device__ __forceinline__ void query_tile(const QueryCtx &S, const int *cand_li
         const int k = cand_list[has ? idx : 0];
         float F[13], Cn[12], lx, ly, lz, cx, cy, cz;
         load_frames(S, k, F, Cn);
-        exact_local(F, px, py, pz, lx, ly, lz);
-        exact_canonical(Cn, F[12], lx, ly, lz, cx, cy, cz);
-        const bool v = active && has && in_unit_cube_incl(lx, ly, lz) && in_unit_cube_strict(cx, cy, cz);
+        part_point(F, Cn, px, py, pz, lx, ly, lz, cx, cy, cz);
+        const bool v = active && has && ENARF_POINT_IN_PART(lx, ly, lz, cx, cy, cz);
         if (v) mine |= (1u << k);
         if (DBG && active && has) {
             if (dbg.canonical) {
@@ -608,8 +595,7 @@ __device__ __forceinline__ void query_tile(const QueryCtx &S, const int *cand_li
         rem &= rem - 1;
         float F[13], Cn[12], lx, ly, lz, cx, cy, cz;
         load_frames(S, k, F, Cn);
-        exact_local(F, px, py, pz, lx, ly, lz);
-        exact_canonical(Cn, F[12], lx, ly, lz, cx, cy, cz);
+        part_point(F, Cn, px, py, pz, lx, ly, lz, cx, cy, cz);
         // lane g owns plane g: xy, yz, zx (lane 3 repeats plane 0 and is ignored)
         const float qx = (g == 1) ? cy : (g == 2) ? cz : cx;
         const float qy = (g == 1) ? cz : (g == 2) ? cx : cy;

@@ -28,6 +28,8 @@
 
 namespace {
 
+using enarf::host::align256;
+
 constexpr int kBlock = 256;
 constexpr int kBigPixels = 256;       // a bounding box above this many pixel centres goes to raster_big_kernel
 constexpr int kBigBlocks = 1024;
@@ -40,8 +42,6 @@ struct Layout {
     long long cap;                    // slots: at most min(V, 3 R^2) vertices belong to a winning triangle
     size_t pxy, pz, keys, slot, ctr, big, svert, cnt, off, nrm, list, bytes;
 };
-
-inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
 inline Layout layout(long long V, long long T, int R) {
     Layout l;

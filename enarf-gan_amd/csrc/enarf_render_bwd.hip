@@ -167,9 +167,8 @@ __device__ __forceinline__ void bwd_gather_tile(const QueryCtx &S, const BwdTile
             const int k = l_cand[has ? idx : 0];
             float F[13], Cn[12], lx, ly, lz, cx, cy, cz;
             load_frames(S, k, F, Cn);
-            exact_local(F, px, py, pz, lx, ly, lz);
-            exact_canonical(Cn, F[12], lx, ly, lz, cx, cy, cz);
-            if (active && has && in_unit_cube_incl(lx, ly, lz) && in_unit_cube_strict(cx, cy, cz)) mine |= (1u << k);
+            part_point(F, Cn, px, py, pz, lx, ly, lz, cx, cy, cz);
+            if (active && has && ENARF_POINT_IN_PART(lx, ly, lz, cx, cy, cz)) mine |= (1u << k);
         }
         bits = mine | (uint32_t)quad_perm_i<0xB1>((int)mine);
         bits |= (uint32_t)quad_perm_i<0x4E>((int)bits);
@@ -184,8 +183,7 @@ __device__ __forceinline__ void bwd_gather_tile(const QueryCtx &S, const BwdTile
             rem &= rem - 1;
             float F[13], Cn[12], lx, ly, lz, cx, cy, cz;
             load_frames(S, k, F, Cn);
-            exact_local(F, px, py, pz, lx, ly, lz);
-            exact_canonical(Cn, F[12], lx, ly, lz, cx, cy, cz);
+            part_point(F, Cn, px, py, pz, lx, ly, lz, cx, cy, cz);
             const float qx = (g4 == 1) ? cy : (g4 == 2) ? cz : cx;
             const float qy = (g4 == 1) ? cz : (g4 == 2) ? cx : cy;
             const Taps t = make_taps(qx, qy, T.H, T.W);
@@ -256,8 +254,7 @@ __device__ __forceinline__ void bwd_backward_tile(const QueryCtx &S, const BwdTi
     auto round_taps = [&](int k) {      // this lane's own-plane taps of part k at the sample (lane 3 repeats plane 0)
         float F[13], Cn[12], lx, ly, lz, cx, cy, cz;
         load_frames(S, k, F, Cn);
-        exact_local(F, px, py, pz, lx, ly, lz);
-        exact_canonical(Cn, F[12], lx, ly, lz, cx, cy, cz);
+        part_point(F, Cn, px, py, pz, lx, ly, lz, cx, cy, cz);
         const float qx = (g4 == 1) ? cy : (g4 == 2) ? cz : cx;
         const float qy = (g4 == 1) ? cz : (g4 == 2) ? cx : cy;
         return make_taps(qx, qy, T.H, T.W);
@@ -366,13 +363,7 @@ __device__ __forceinline__ void bwd_stage_image(const void *mlp_pack, const floa
     for (int i = tid; i < PK_B1 / 4; i += 256) reinterpret_cast<f32x4 *>(l_w)[i] = reinterpret_cast<const f32x4 *>(pf)[i];
     for (int i = tid; i < 144; i += 256) l_bias[i] = pf[PK_B1 + i];
     for (int i = tid; i < PKT_FLOATS / 4; i += 256) reinterpret_cast<f32x4 *>(l_wt)[i] = reinterpret_cast<const f32x4 *>(pt)[i];
-    const float *parts_b = parts + (size_t)b * P * kPartStride;
-    for (int i = tid; i < P * kPartStride; i += 256)
-        l_parts[(i / kPartStride) * kLdsPartStride + (i % kPartStride)] = parts_b[i];
-    for (int i = tid; i < P * 12; i += 256) {
-        const int k = i / 12, e = i % 12;
-        l_canon[i] = (e < 9) ? canonical_pose[k * 16 + (e / 3) * 4 + (e % 3)] : canonical_pose[k * 16 + (e - 9) * 4 + 3];
-    }
+    stage_frames(l_parts, l_canon, parts + (size_t)b * P * kPartStride, canonical_pose, P, tid, 256);
 }
 
 // SPL = fine tiles per wave: 1 for Nf <= 64 (the activations of the tile stay in registers from F1 to F3), 2 for

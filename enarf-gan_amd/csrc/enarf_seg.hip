@@ -1,7 +1,7 @@
 // enarf_seg.hip - libenarf_seg.so: part segmentation (gfx950 / CDNA4 only, wave64). The contract is in include/enarf_seg.h.
 //
-//   seg_label_kernel      one lane per point: the bone transforms and cube tests of the query and the march (the exact_*
-//                         functions of enarf_device.h, so the validity bits are theirs bit for bit), the part probability
+//   seg_label_kernel      one lane per point: the bone transforms and cube tests of the query and the march (the walk of
+//                         enarf_parts.h, so the validity bits are theirs bit for bit), the part probability
 //                         of every valid pair, and a running best / runner-up - no feature gather, no MLP, no per-part
 //                         array. Consecutive lanes take consecutive samples of a ray, so validity is coherent in a wave.
 //   seg_composite_kernel  one wavefront per ray, lanes as samples: the semantic colour, and the per-part masses by
@@ -9,8 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "enarf_seg.h"
-#include "enarf_device.h"
-#include "enarf_query.h"
+#include "enarf_parts.h"
 #include "enarf_host.h"
 
 namespace {
@@ -21,32 +20,12 @@ constexpr int kBlock = 256;
 constexpr int kMaxParts = ENARF_SEG_MAX_PARTS;
 static_assert(kMaxParts == ENARF_MAX_PARTS, "the bit mask of the march");
 
-// sigmoid(bilinear(plane)) of one part-probability plane at (x, y): make_taps + two row pairs, as enarf_query.h:614-644
-__device__ __forceinline__ float plane_sigmoid(const char *__restrict__ maskb, unsigned plane_off, float x, float y, int H,
-                                               int W, int clamp_mask) {
-    const Taps t = make_taps(x, y, H, W);
-    float m00, m01, m10, m11;
-    load_row_pair(maskb, plane_off, t.o00, t.xe, m00, m01);
-    load_row_pair(maskb, plane_off, t.o10, t.xe, m10, m11);
-    float macc = m00 * t.w00;
-    macc += m01 * t.w01;
-    macc += m10 * t.w10;
-    macc += m11 * t.w11;
-    if (clamp_mask) macc = fminf(fmaxf(macc, -2.0f), 5.0f);
-    return sigmoidf_(macc);
-}
-
 __global__ void __launch_bounds__(kBlock) seg_label_kernel(const enarf_seg_label_args a) {
     __shared__ __attribute__((aligned(16))) float l_parts[kMaxParts * kLdsPartStride];
     __shared__ __attribute__((aligned(16))) float l_canon[kMaxParts * kLdsCanonStride];
     const int tid = threadIdx.x, b = blockIdx.y, P = a.P;
     const float *parts_b = a.parts + (size_t)b * P * kPartStride;
-    for (int i = tid; i < P * kPartStride; i += kBlock)
-        l_parts[(i / kPartStride) * kLdsPartStride + (i % kPartStride)] = parts_b[i];
-    for (int i = tid; i < P * 12; i += kBlock) {   // (P,4,4) -> Rc row-major 9 + tc 3
-        const int k = i / 12, e = i % 12;
-        l_canon[i] = (e < 9) ? a.canonical_pose[k * 16 + (e / 3) * 4 + (e % 3)] : a.canonical_pose[k * 16 + (e - 9) * 4 + 3];
-    }
+    stage_frames(l_parts, l_canon, parts_b, a.canonical_pose, P, tid, kBlock);
     __syncthreads();
     const long long i = (long long)blockIdx.x * kBlock + tid;
     if (i >= a.M) return;
@@ -79,27 +58,12 @@ __global__ void __launch_bounds__(kBlock) seg_label_kernel(const enarf_seg_label
     float best = -1.0f, second = -1.0f;
     for (int k = 0; k < P; ++k) {
         float F[13], Cn[12], lx, ly, lz, cx, cy, cz;
-        const f32x4 *pf = reinterpret_cast<const f32x4 *>(l_parts + k * kLdsPartStride);
-        const f32x4 *pc = reinterpret_cast<const f32x4 *>(l_canon + k * kLdsCanonStride);
-        const f32x4 f0 = pf[0], f1 = pf[1], f2 = pf[2], f3 = pf[3];
-        const f32x4 c0 = pc[0], c1 = pc[1], c2 = pc[2];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { F[j] = f0[j]; F[4 + j] = f1[j]; F[8 + j] = f2[j]; }
-        F[12] = f3[0];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { Cn[j] = c0[j]; Cn[4 + j] = c1[j]; Cn[8 + j] = c2[j]; }
-        exact_local(F, px, py, pz, lx, ly, lz);
-        exact_canonical(Cn, F[12], lx, ly, lz, cx, cy, cz);
-        if (!(in_unit_cube_incl(lx, ly, lz) && in_unit_cube_strict(cx, cy, cz))) continue;
+        load_frames(l_parts, l_canon, k, F, Cn);
+        part_point(F, Cn, px, py, pz, lx, ly, lz, cx, cy, cz);
+        if (!ENARF_POINT_IN_PART(lx, ly, lz, cx, cy, cz)) continue;
         bits |= 1u << k;
         float w = uniform_w;
-        if (!a.uniform_part_weight) {      // planes xy, yz, zx of part k
-            const unsigned off = (unsigned)(3 * k) * plane_bytes;
-            const float s0 = plane_sigmoid(maskb, off, cx, cy, a.H, a.W, a.clamp_mask);
-            const float s1 = plane_sigmoid(maskb, off + plane_bytes, cy, cz, a.H, a.W, a.clamp_mask);
-            const float s2 = plane_sigmoid(maskb, off + 2u * plane_bytes, cz, cx, a.H, a.W, a.clamp_mask);
-            w = (s0 * s1) * s2;
-        }
+        if (!a.uniform_part_weight) w = part_probability(maskb, k, plane_bytes, cx, cy, cz, a.H, a.W, a.clamp_mask);
         if (w > best) {                    // strictly: the lowest index wins a tie
             second = best;
             best = w;
@@ -179,10 +143,7 @@ int enarf_seg_labels(const enarf_seg_label_args *args, void *stream) {
     const char *who = "enarf_seg_labels";
     if (!args) return enarf::host::fail(ENARF_ERR_ARG, "%s: null args", who);
     const enarf_seg_label_args &a = *args;
-    if (a.P < 1 || a.P > kMaxParts) return enarf::host::fail(ENARF_ERR_ARG, "%s: %d parts outside [1, %d]", who, a.P, kMaxParts);
-    if (a.H < 2 || a.W < 2 || 3LL * a.P * a.H * a.W >= (1LL << 30))
-        return enarf::host::fail(ENARF_ERR_ARG, "%s: planes %d x %d with %d parts: H, W >= 2 and 3 P H W < 2^30 floats", who, a.H,
-                                 a.W, a.P);
+    if (const int e = enarf::host::check_part_planes(who, a.P, kMaxParts, a.H, a.W)) return e;
     if (a.B < 0 || a.B > 65535) return enarf::host::fail(ENARF_ERR_ARG, "%s: batch %d outside [0, 65535]", who, a.B);
     if (a.M < 0 || a.M / kBlock + 1 >= (1LL << 31)) return enarf::host::fail(ENARF_ERR_ARG, "%s: %lld points a image", who, (long long)a.M);
     if (a.mask_batch_stride < 0) return enarf::host::fail(ENARF_ERR_ARG, "%s: negative mask batch stride", who);

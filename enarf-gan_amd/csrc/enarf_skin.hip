@@ -1,16 +1,15 @@
 // enarf_skin.hip - libenarf_skin.so: rigged meshes (gfx950 / CDNA4 only, wave64). The contract is in include/enarf_skin.h.
 //
 //   skin_weights_kernel<K>  one lane per vertex: the bone transforms and cube tests of the query and the march (the
-//                           exact_* functions of enarf_device.h, so the validity bits are theirs bit for bit), the part
-//                           probability of every valid pair as seg_label_kernel forms it, and the K largest kept by
+//                           walk of enarf_parts.h, so the validity bits are theirs bit for bit), the part probability
+//                           of every valid pair as seg_label_kernel forms it, and the K largest kept by
 //                           sorted insertion into K registers - no feature gather, no MLP, no per-part array.
 //   skin_pose_kernel<K>     one lane per vertex, a workgroup per (256 vertices, 8 frames): the frames' part transforms
 //                           staged in LDS in fp64, the vertex, its joints and weights read once, one fp64 blend a frame.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "enarf_skin.h"
-#include "enarf_device.h"
-#include "enarf_query.h"
+#include "enarf_parts.h"
 #include "enarf_host.h"
 
 namespace {
@@ -24,32 +23,12 @@ constexpr int kXf = 12;                 // doubles a transform: L row-major 9, t
 static_assert(kMaxParts == ENARF_MAX_PARTS, "the bit mask of the march");
 static_assert(kFrames * kMaxParts <= kBlock, "one lane stages one transform");
 
-// sigmoid(bilinear(plane)) of one part-probability plane at (x, y): seg_label_kernel's (enarf_seg.hip), operation for operation
-__device__ __forceinline__ float plane_sigmoid(const char *__restrict__ maskb, unsigned plane_off, float x, float y, int H,
-                                               int W, int clamp_mask) {
-    const Taps t = make_taps(x, y, H, W);
-    float m00, m01, m10, m11;
-    load_row_pair(maskb, plane_off, t.o00, t.xe, m00, m01);
-    load_row_pair(maskb, plane_off, t.o10, t.xe, m10, m11);
-    float macc = m00 * t.w00;
-    macc += m01 * t.w01;
-    macc += m10 * t.w10;
-    macc += m11 * t.w11;
-    if (clamp_mask) macc = fminf(fmaxf(macc, -2.0f), 5.0f);
-    return sigmoidf_(macc);
-}
-
 template <int K>
 __global__ void __launch_bounds__(kBlock) skin_weights_kernel(const enarf_skin_weights_args a) {
     __shared__ __attribute__((aligned(16))) float l_parts[kMaxParts * kLdsPartStride];
     __shared__ __attribute__((aligned(16))) float l_canon[kMaxParts * kLdsCanonStride];
     const int tid = threadIdx.x, P = a.P;
-    for (int i = tid; i < P * kPartStride; i += kBlock)
-        l_parts[(i / kPartStride) * kLdsPartStride + (i % kPartStride)] = a.parts[i];
-    for (int i = tid; i < P * 12; i += kBlock) {   // (P,4,4) -> Rc row-major 9 + tc 3
-        const int k = i / 12, e = i % 12;
-        l_canon[i] = (e < 9) ? a.canonical_pose[k * 16 + (e / 3) * 4 + (e % 3)] : a.canonical_pose[k * 16 + (e - 9) * 4 + 3];
-    }
+    stage_frames(l_parts, l_canon, a.parts, a.canonical_pose, P, tid, kBlock);
     __syncthreads();
     const long long i = (long long)blockIdx.x * kBlock + tid;
     if (i >= a.V) return;
@@ -69,30 +48,15 @@ __global__ void __launch_bounds__(kBlock) skin_weights_kernel(const enarf_skin_w
     for (int j = 0; j < K; ++j) { jk[j] = -1; wk[j] = -1.0f; }
     for (int k = 0; k < P; ++k) {
         float F[13], Cn[12], lx, ly, lz, cx, cy, cz;
-        const f32x4 *pf = reinterpret_cast<const f32x4 *>(l_parts + k * kLdsPartStride);
-        const f32x4 *pc = reinterpret_cast<const f32x4 *>(l_canon + k * kLdsCanonStride);
-        const f32x4 f0 = pf[0], f1 = pf[1], f2 = pf[2], f3 = pf[3];
-        const f32x4 c0 = pc[0], c1 = pc[1], c2 = pc[2];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { F[j] = f0[j]; F[4 + j] = f1[j]; F[8 + j] = f2[j]; }
-        F[12] = f3[0];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { Cn[j] = c0[j]; Cn[4 + j] = c1[j]; Cn[8 + j] = c2[j]; }
-        exact_local(F, px, py, pz, lx, ly, lz);
-        exact_canonical(Cn, F[12], lx, ly, lz, cx, cy, cz);
+        load_frames(l_parts, l_canon, k, F, Cn);
+        part_point(F, Cn, px, py, pz, lx, ly, lz, cx, cy, cz);
         const float d = fmaxf(fmaxf(fabsf(lx), fabsf(ly)), fabsf(lz));
         if (d < near_d) { near_d = d; near_k = k; }          // strictly: the lowest index wins a tie
-        if (!(in_unit_cube_incl(lx, ly, lz) && in_unit_cube_strict(cx, cy, cz))) continue;
+        if (!ENARF_POINT_IN_PART(lx, ly, lz, cx, cy, cz)) continue;
         bits |= 1u << k;
         ++n_valid;
         float w = uniform_w;
-        if (!a.uniform_part_weight) {      // planes xy, yz, zx of part k
-            const unsigned off = (unsigned)(3 * k) * plane_bytes;
-            const float s0 = plane_sigmoid(maskb, off, cx, cy, a.H, a.W, a.clamp_mask);
-            const float s1 = plane_sigmoid(maskb, off + plane_bytes, cy, cz, a.H, a.W, a.clamp_mask);
-            const float s2 = plane_sigmoid(maskb, off + 2u * plane_bytes, cz, cx, a.H, a.W, a.clamp_mask);
-            w = (s0 * s1) * s2;
-        }
+        if (!a.uniform_part_weight) w = part_probability(maskb, k, plane_bytes, cx, cy, cz, a.H, a.W, a.clamp_mask);
         total += (double)w;
         // sorted insertion: the newcomer passes every slot it does not strictly beat, then pushes the rest down one
         float cw = w;
@@ -226,10 +190,7 @@ int enarf_skin_weights(const enarf_skin_weights_args *args, void *stream) {
     const enarf_skin_weights_args &a = *args;
     if (a.max_influences != 4 && a.max_influences != 8)
         return enarf::host::fail(ENARF_ERR_ARG, "%s: max_influences %d, takes 4 or 8", who, a.max_influences);
-    if (a.P < 1 || a.P > kMaxParts) return enarf::host::fail(ENARF_ERR_ARG, "%s: %d parts outside [1, %d]", who, a.P, kMaxParts);
-    if (a.H < 2 || a.W < 2 || 3LL * a.P * a.H * a.W >= (1LL << 30))
-        return enarf::host::fail(ENARF_ERR_ARG, "%s: planes %d x %d with %d parts: H, W >= 2 and 3 P H W < 2^30 floats", who, a.H,
-                                 a.W, a.P);
+    if (const int e = enarf::host::check_part_planes(who, a.P, kMaxParts, a.H, a.W)) return e;
     if (a.V < 0 || a.V / kBlock + 1 >= (1LL << 31)) return enarf::host::fail(ENARF_ERR_ARG, "%s: %lld vertices", who, (long long)a.V);
     if (a.vert_stride < 0 || a.comp_stride < 0) return enarf::host::fail(ENARF_ERR_ARG, "%s: negative vertex strides", who);
     if (a.V == 0) return 0;

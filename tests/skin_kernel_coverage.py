@@ -7,7 +7,8 @@ _NS = "void (anonymous namespace)::"
 _WEIGHT_TESTS = ["test_gpu_skin::test_weights_on_scene_points_match_the_referee",
                  "test_gpu_skin::test_weights_on_explicit_vertices_tails_and_both_layouts",
                  "test_gpu_skin::test_weights_on_cube_faces_and_far_outside_every_cube",
-                 "test_gpu_skin::test_six_coincident_parts_bit_for_bit"]
+                 "test_gpu_skin::test_six_coincident_parts_bit_for_bit",
+                 "test_gpu_skin::test_skin_and_seg_agree_on_membership"]
 _POSE_TESTS = ["test_gpu_skin::test_posing_matches_the_referee_to_one_fp32_step",
                "test_gpu_skin::test_posing_writes_into_a_slice_and_repeats_bit_for_bit"]
 SKIN_KERNEL_TESTS = {

@@ -49,6 +49,12 @@ def _weights(ds, pts, K, **kw):
                             coordinate_scale=1.0, return_valid_bits=True, **kw)
 
 
+def _far_points(sc, n=300):
+    """(1, 3, n) points 50 units from the first part: outside every cube"""
+    far = torch.randn(1, 3, n, generator=torch.Generator().manual_seed(0))
+    return (far / far.norm(dim=1, keepdim=True) * 50.0 + sc.pose_scaled[0, 0, :3, 3][None, :, None]).contiguous()
+
+
 def _check_weights(got, ref, P, K, what, cap):
     joints, weights, mass, bits = (_np(t) for t in got)
     N = len(ref["n_valid"])
@@ -146,9 +152,7 @@ def test_weights_on_cube_faces_and_far_outside_every_cube(K):
     valid = torch.from_numpy(ref["valid"])[None]
     assert int((on_face & valid).sum()) > 100 and int((on_face & ~valid).sum()) > 100
     _check_weights(_weights(ds, pts, K), ref, sc.P, K, f"faces K={K}", cap=False)
-    g = torch.Generator().manual_seed(0)
-    far = torch.randn(1, 3, 300, generator=g)
-    far = (far / far.norm(dim=1, keepdim=True) * 50.0 + sc.pose_scaled[0, 0, :3, 3][None, :, None]).contiguous()
+    far = _far_points(sc)
     fref = SK.weights(far, sc.pose_scaled, sc.scale, sc.cpose, sc.raw["tri_plane"], K)
     assert fref["unowned"].all() and len(np.unique(fref["fallback"])) >= 3
     joints, weights, mass, bits = _weights(ds, far, K)
@@ -156,6 +160,31 @@ def test_weights_on_cube_faces_and_far_outside_every_cube(K):
     assert bool((weights[:, 0] == 1).all()) and bool((weights[:, 1:] == 0).all()) and bool((mass == 0).all()) and bool((bits == 0).all())
     empty = ops.skin_weights(torch.zeros(0, 3, device=ds.dev), ds.parts, ds.cpose, ds.tri, max_influences=K, return_valid_bits=True)
     assert [tuple(t.shape) for t in empty] == [(0, K), (0, K), (0,), (0,)] and empty[0].dtype == torch.int32
+
+
+@pytest.mark.parametrize("K", [4, 8])
+def test_skin_and_seg_agree_on_membership(K):
+    """skin_weights_kernel and seg_label_kernel walk the parts through the one definition in csrc/enarf_parts.h: on the same
+    300 points (a full 256-lane block and a tail: scene points, points on and a few ulp off the cube faces, points outside
+    every cube) their validity bits are equal, the strongest influence is the label (both let the lowest index win a tie),
+    and a point no part contains has label -1 and kept mass 0"""
+    from enarf_gan_amd import ops
+    from test_gpu_parity import _cube_face_points
+    sc, ds = _scene("center_fixed")
+    scene, faces = SK.scene_points(sc), _cube_face_points(sc, per=2000, seed=5)
+    pick = lambda p, n: p[0, :, torch.linspace(0, p.shape[2] - 1, n).long()]
+    v = torch.cat([pick(scene, 180), pick(faces, 80), _far_points(sc)[0, :, :40]], dim=1).t().contiguous().to(ds.dev)
+    assert v.shape == (300, 3)
+    for flags in ({}, {"uniform_part_weight": True}):
+        joints, _, mass, bits = ops.skin_weights(v, ds.parts, ds.cpose, ds.tri, max_influences=K, coordinate_scale=1.0,
+                                                 return_valid_bits=True, **flags)
+        label, _, _, seg_bits = ops.part_labels(v, ds.parts, ds.cpose, ds.tri, points_last=True, return_valid_bits=True, **flags)
+        label, seg_bits = label.reshape(-1), seg_bits.reshape(-1)
+        assert torch.equal(bits, seg_bits), flags
+        owned = bits != 0
+        assert int(owned.sum()) >= 100 and int((~owned).sum()) >= 40, "both kinds of point are present"
+        assert torch.equal(joints[owned, 0], label[owned]), flags
+        assert bool((label[~owned] == -1).all()) and bool((mass[~owned] == 0).all()), flags
 
 
 @pytest.mark.parametrize("K", [4, 8])

@@ -40,6 +40,7 @@ SIDE_LIBRARIES = {
     "seg": (["enarf_seg.hip"], "enarf_seg.h"),             # part labels of sample points and the semantic map of a frame
     "paint": (["enarf_paint.hip"], "enarf_paint.h"),       # deferred shading of a rasterised mesh: vertex colours, part labels
     "geom": (["enarf_geom.hip"], "enarf_geom.h"),          # depth, point and normal maps of a march, running depth error
+    "pgrad": (["enarf_pgrad.hip"], "enarf_pgrad.h"),       # the query's gradient for the sample points and the part frames
     "skin": (["enarf_skin.hip"], "enarf_skin.h"),          # skin weights of mesh vertices, linear-blend posing of the mesh
 }
 ALL_LIBRARIES = {**LIBRARIES, **SIDE_LIBRARIES}

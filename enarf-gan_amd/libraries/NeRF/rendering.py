@@ -250,3 +250,65 @@ def render_entire_img(model, pose_to_camera: torch.Tensor, inv_intrinsics: torch
                                         semantic_map=semantic_map, camera_pose=camera_pose, model_input=mi)
     return (color.reshape(3, render_height, render_width), mask.reshape(render_height, render_width),
             disparity.reshape(render_height, render_width))
+
+
+def composite_fine(density: torch.Tensor, color: torch.Tensor, depth: torch.Tensor, render_scale: float = 1.0):
+    """The reference's alpha compositing of the fine samples (rendering.py:307-335) in torch, on any device and dtype:
+    density (B, n, Nf), color (B, 3, n, Nf), depth (B, n, Nf) -> colour (B, 3, n), mask (B, n), disparity (B, n), weights
+    (B, n, Nf - 1). The first Nf - 1 samples are integrated; sample i spans depth[i + 1] - depth[i]."""
+    delta = depth[..., 1:] - depth[..., :-1]
+    dd = density[..., :-1] * delta * render_scale
+    transmittance = torch.exp(-(torch.cumsum(dd, dim=-1) - dd))
+    w = transmittance * (1 - torch.exp(-dd))
+    return (w[:, None] * color[..., :-1]).sum(dim=-1), w.sum(dim=-1), (w * 1 / depth[..., :-1]).sum(dim=-1), w
+
+
+def render_posable(model, image_coord: torch.Tensor, pose_to_camera: torch.Tensor, inv_intrinsics: torch.Tensor,
+                   render_scale: float = 1, Nc: int = 64, Nf: int = 128, model_input: Dict = {},
+                   bins: Optional[torch.Tensor] = None, seed: Optional[int] = None):
+    """render() for a pose that requires gradients: image_coord (B, 1, 3, n); pose_to_camera (B, P, 4, 4) part frames
+    (translation not yet scaled, as render takes them); model_input["bone_length"] the parts' bone lengths ->
+    (colour (B, 3, n), mask (B, n), disparity (B, n)), differentiable with respect to pose_to_camera and bone_length, and
+    to the tri-plane, z_rend and the StyledMLP where they require gradients.
+
+    Contract: the gradient is that of the image AT FIXED SAMPLE POSITIONS. One march under no_grad (the fused kernel, its
+    taps) fixes every ray's depth range, its validity and its importance samples; the fine points are formed from them as
+    return_intermediate forms them and are constants. model.query_posable at those points and the reference's compositing
+    (composite_fine) carry the gradient. The reference detaches its importance samples as well; what is ignored here
+    beyond that is the dependence of a ray's depth range on the pose. The forward values are those of
+    render() on the same bins up to the rounding of the compositing sums. A ray the march drops (one image, no cube hit)
+    is zero."""
+    assert pose_to_camera.shape[1] == model.num_bone
+    B, n = image_coord.shape[0], image_coord.shape[-1]
+    cs = model.coordinate_scale
+    z_rend = model_input["z_rend"]
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    with torch.no_grad():
+        parts = _parts_from_part_poses(model, pose_to_camera.detach(), model_input["bone_length"].detach())
+        mi = dict(model_input)
+        tri, feat_cl = model._tri_plane_pair(mi)
+        out = ops.render_fwd(image_coord, inv_intrinsics, parts, model.canonical_pose, tri, feat_cl,
+                             model._mlp_pack(z_rend.detach()), Nc, Nf, render_scale=render_scale, bins=bins, seed=seed,
+                             mlp_mode=model.mlp_mode, debug=True, **model.kernel_flags())
+        t = out.taps
+        coord = image_coord.reshape(B, 3, n).to(torch.float32)
+        Ki = inv_intrinsics.to(torch.float32)
+        if Ki.dim() == 2:
+            Ki = Ki[None].expand(B, -1, -1)
+        ray = torch.einsum("bij,bjn->bin", Ki, coord)
+        b_ = t["bins"][:, None]                                                # (B, 1, n, Nf)
+        start, end = (t["depth_min"][:, None] * ray)[..., None], (t["depth_max"][:, None] * ray)[..., None]
+        fine_points = (start * (1 - b_) + end * b_).reshape(B, 3, n * Nf)
+        fine_depth = t["depth_min"][..., None] * (1 - t["bins"]) + t["depth_max"][..., None] * t["bins"]
+        live = t["ray_validity"].to(torch.float32) if B == 1 else None         # rendering.py:107-110
+    frames = torch.cat([pose_to_camera[:, :, :3, :3], pose_to_camera[:, :, :3, 3:] * cs], dim=-1)
+    density, color = model.query_posable(fine_points, frames, model_input)
+    rc, rm, rd, w = composite_fine(density.reshape(B, n, Nf), color.reshape(B, 3, n, Nf), fine_depth, render_scale)
+    if live is not None:
+        rc, rm, rd = rc * live[:, None], rm * live, rd * live
+    if not hasattr(model, "buffers_tensors"):
+        model.buffers_tensors = {}
+    model.buffers_tensors.update(bins=t["bins"], fine_depth=fine_depth[:, None], fine_weights=w.detach()[:, None],
+                                 fine_points=fine_points)
+    return rc, rm, rd

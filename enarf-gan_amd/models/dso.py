@@ -30,6 +30,33 @@ def train_step(gen, loss_func, batch: Dict[str, torch.Tensor], optimizer, bg_col
     return loss_color.detach(), loss_mask.detach()
 
 
+def train_step_posable(gen, loss_func, batch: Dict[str, torch.Tensor], optimizer, bg_color: float, correction,
+                       pose_optimizer):
+    """train_step with the poses of the sequence refined while the scene is learned: the batch's 24-joint poses pass
+    through `correction` (models.fit.PoseCorrection; batch["frame_idx"] (B,) int64 names each image's frame, default
+    image b = frame b) and the rays are rendered by render_posable, whose gradient reaches the correction's residuals as
+    well as the field's parameters; `optimizer` steps the field, `pose_optimizer` the correction. The latents are formed
+    from the poses as given (a pose-conditional latent does not see the correction). The gradient is that of the image
+    at fixed sample positions (render_posable). Returns (loss_color, loss_mask) as detached device scalars - nothing here
+    synchronises."""
+    from ..libraries.NeRF.rendering import render_posable
+    gen.train()
+    img, mask, pose_to_camera, frame_time, bone_length, _camera_rotation, inv_intrinsic = _unpack(batch)
+    optimizer.zero_grad()
+    pose_optimizer.zero_grad()
+    ray_idx, pixels = gen.ray_sampler(mask, gen.config.ray_batchsize)
+    z_tri, z_render = gen.get_latents(frame_time, pose_to_camera)
+    pose_parts, bl_parts = gen.nerf.transform_pose(correction(pose_to_camera, batch.get("frame_idx")), bone_length)
+    model_input = {"z": z_tri, "z_rend": z_render, "bone_length": bl_parts, "truncation_psi": 1}
+    color, alpha, _ = render_posable(gen.nerf, pixels, pose_parts, inv_intrinsic, model_input=model_input, **gen._samples)
+    nerf_color = color + bg_color * (1 - alpha[:, None])
+    loss_color, loss_mask = loss_func(ray_idx, nerf_color, alpha, img, mask)
+    (loss_color + loss_mask).backward()
+    optimizer.step()
+    pose_optimizer.step()
+    return loss_color.detach(), loss_mask.detach()
+
+
 def _mask_bbox(mask: torch.Tensor):
     """train_DSO.py:108-119: (x_min, y_min, x_max, y_max) of the first and last foreground column / row (the last ones
     are left out of the slices, as there), or None for an empty mask. Reads the mask back: cropping needs host sizes."""

@@ -474,6 +474,26 @@ class TriPlaneNARF(nn.Module):
             self.temporal_state["valid_bits"] = vb
         return den, col
 
+    def query_posable(self, position: torch.Tensor, pose_to_camera: torch.Tensor, model_input: Dict):
+        """The query of calc_density_and_color_from_camera_coord_v2, differentiable with respect to its articulation:
+        position (B,3,n) camera coords, pose_to_camera (B,P,4,4) part frames whose translation is already x
+        coordinate_scale, model_input["bone_length"] the parts' (B,P,1) bone lengths -> density (B,1,n), colour (B,3,n),
+        the outputs of ops.query_fwd (mode f32) bit for bit. position, pose_to_camera and bone_length receive gradients
+        (ops.query_pose_bwd; the (B,P,16) part records are assembled in torch, so whatever produced the frames - the 24
+        joints through transform_pose, a pose correction - is differentiated by torch's own graph); the tri-plane, z_rend
+        and the StyledMLP receive theirs through ops.query_bwd where they require them. The gradient is the one the
+        reference's autograd would return: the cube tests and the bilinear cells are constants, and the density
+        activation keeps its own backward rule."""
+        B, P = pose_to_camera.shape[:2]
+        scale = (self.canonical_bone_length[:, None] / model_input["bone_length"] / self.coordinate_scale)[:, :, 0]
+        parts = torch.cat([pose_to_camera[:, :, :3, :3].reshape(B, P, 9), pose_to_camera[:, :, :3, 3], scale[:, :, None],
+                           scale.new_zeros(B, P, 3)], dim=2).float()
+        z_rend = model_input["z_rend"]
+        params = self.mlp.as_dict()
+        k = dict(canonical_pose=self.canonical_pose, pack_fn=self._mlp_pack_from, flags=self.kernel_flags())
+        flat = [params[f"layers.{i}.{leaf}"] for i in range(3) for leaf in _MLP_LEAVES]
+        return _PosableQueryFunction.apply(k, position.float(), parts, self._tri_plane_graph(model_input), z_rend, *flat)
+
 
 _MLP_LEAVES = ("conv.weight", "conv.modulation.weight", "conv.modulation.bias", "bias")
 
@@ -559,3 +579,42 @@ class _QueryFunction(torch.autograd.Function):
             grads += [pg[f"layers.{i}.conv.weight"], pg[f"layers.{i}.conv.modulation.weight"],
                       pg[f"layers.{i}.conv.modulation.bias"], db[i].reshape(params[4 * i + 3].shape)]
         return (None, grad_tri, dz) + tuple(grads)
+
+
+class _PosableQueryFunction(torch.autograd.Function):
+    """_QueryFunction (mode f32) that also differentiates the sample points and the (B,P,16) part records: backward =
+    enarf_pgrad_query, and enarf_query_bwd + enarf_weight_grad + enarf_prepare_bwd where the tri-plane, z_rend or a
+    StyledMLP tensor requires a gradient too."""
+
+    @staticmethod
+    def forward(ctx, k, points, parts, tri, z_rend, *params):
+        mlp = {f"layers.{i}.{leaf}": params[4 * i + j].detach() for i in range(3) for j, leaf in enumerate(_MLP_LEAVES)}
+        pts, prt, tri_c = points.detach().contiguous(), parts.detach().contiguous(), tri.detach().contiguous()
+        feat_cl = ops.triplane_pack(tri_c)
+        pack = k["pack_fn"](z_rend.detach(), mlp)
+        den, col = ops.query_fwd(pts, prt, k["canonical_pose"], tri_c, feat_cl, pack, mlp_mode="f32", **k["flags"])
+        ctx.k = k
+        ctx.save_for_backward(pts, prt, tri_c, feat_cl, pack, z_rend.detach(), *mlp.values())
+        return den, col
+
+    @staticmethod
+    def backward(ctx, g_den, g_col):
+        k = ctx.k
+        pts, prt, tri_c, feat_cl, pack, z_rend = ctx.saved_tensors[:6]
+        params = ctx.saved_tensors[6:]
+        g_den = None if g_den is None else g_den.contiguous()
+        g_col = None if g_col is None else g_col.contiguous()
+        g_points = g_parts = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            g_points, g_parts = ops.query_pose_bwd(pts, prt, k["canonical_pose"], tri_c, feat_cl, pack, g_den, g_col, **k["flags"])
+        rest = (None,) * (2 + len(params))
+        if any(ctx.needs_input_grad[3:]):
+            mlp = {f"layers.{i}.{leaf}": params[4 * i + j] for i in range(3) for j, leaf in enumerate(_MLP_LEAVES)}
+            grad_tri, dW, db = ops.query_bwd(pts, prt, k["canonical_pose"], tri_c, feat_cl, pack, g_den, g_col, **k["flags"])
+            pg, dz = ops.prepare_bwd(z_rend, mlp, dW)
+            grads = []
+            for i in range(3):
+                grads += [pg[f"layers.{i}.conv.weight"], pg[f"layers.{i}.conv.modulation.weight"],
+                          pg[f"layers.{i}.conv.modulation.bias"], db[i].reshape(params[4 * i + 3].shape)]
+            rest = (grad_tri, dz) + tuple(grads)
+        return (None, g_points if ctx.needs_input_grad[1] else None, g_parts if ctx.needs_input_grad[2] else None) + rest

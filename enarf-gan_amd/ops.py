@@ -974,6 +974,24 @@ def skin_pose(vertices: torch.Tensor, joints: torch.Tensor, weights: torch.Tenso
     return _skin_lib.skin_pose(vertices, joints, weights, parts_rest, parts, coordinate_scale, out)
 
 
+# ------------------------------------------------------------------------------------------------- differentiable pose
+def query_pose_bwd(points: torch.Tensor, parts: torch.Tensor, canonical_pose: torch.Tensor, tri_nchw: torch.Tensor,
+                   feat_cl: torch.Tensor, mlp_pack: torch.Tensor, g_density: Optional[torch.Tensor],
+                   g_color: Optional[torch.Tensor], clamp_mask: bool = False, uniform_part_weight: bool = False,
+                   multiply_density_with_weight: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Backward of query_fwd (mode f32) w.r.t. the sample points and the part records, the two inputs query_bwd leaves out,
+    in two launches of libenarf_pgrad.so: (g_points (B, 3, N), g_parts (B, P, 16)) fp32. Arguments as query_fwd / query_bwd
+    take them: points (B, 3, N), parts (B, P, 16) and mlp_pack from prepare, tri_nchw the (1 or B, 96 + 3P, H, W) tri-plane,
+    feat_cl its channel-last feature planes from triplane_pack; g_density (B, N) or (B, 1, N) and g_color (B, 3, N), either
+    of which may be None. g_parts is laid out as the record: dL/dR row-major in 0..8, dL/dt (the scaled translation) in
+    9..11, dL/ds in 12, zeros in 13..15. The gradient is what the reference's autograd returns for its query, the density
+    activation's own backward rule included; validity and the bilinear cells are constants. A point in no cube gets
+    zeros. No atomics: bit-identical from run to run; nothing synchronises. ValueError for shapes it does not take."""
+    from . import _pgrad_lib
+    return _pgrad_lib.query_pose_bwd(points, parts, canonical_pose, tri_nchw, feat_cl, mlp_pack, g_density, g_color,
+                                     clamp_mask, uniform_part_weight, multiply_density_with_weight)
+
+
 # ------------------------------------------------------------------------------------------------- geometry buffers
 from ._geom_lib import DepthError, GeometryBuffers  # noqa: E402,F401  (the running depth error; geometry_buffers' result)
 

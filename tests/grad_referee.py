@@ -95,7 +95,8 @@ def disagreeing_rays(d64, d32):
 def referee(sc, coord, Nc, Nf, bins, gc, gm, gd, tri=None, render_scale=1.0, **modes):
     """The float64 referee and the fp32 yardstick on the same rays, the rays they disagree on excluded (`keep` False).
 
-    Returns dict(out64, out32, g64, g32, keep (B,n) bool tensor, taps32)."""
+    Returns dict(out64, out32, g64, g32, draws, keep (B,n) bool tensor, taps64, taps32, fwd_draws) - fwd_draws: the draws'
+    forward results [(outputs, taps)], which tests/fwd_referee.py holds the forward to."""
     o64, l64, t64 = render_forward(sc, coord, Nc, Nf, bins, torch.float64, tri, render_scale, **modes)
     o32, l32, t32 = render_forward(sc, coord, Nc, Nf, bins, torch.float32, tri, render_scale, **modes)
     keep = torch.from_numpy(~disagreeing_rays(decisions(t64), decisions(t32)))
@@ -103,33 +104,38 @@ def referee(sc, coord, Nc, Nf, bins, gc, gm, gd, tri=None, render_scale=1.0, **m
     g32 = render_grads(o32, l32, gc, gm, gd, keep)
     # more draws of fp32 rounding: every input (bins, tri-plane, MLP parameters, z_rend) moved by up to one ulp, so the
     # fine depths, their differences and every product round another way
-    draws = []
+    draws, fwd_draws = [], []
     for i in range(DRAWS):
         op, lp, tp = render_forward(perturbed_scene(sc, i), coord, Nc, Nf, perturb(bins, 1000 + i).sort(-1).values, torch.float32,
                                     None if tri is None else perturb(tri, 2000 + i), render_scale, **modes)
         keep &= torch.from_numpy(~disagreeing_rays(decisions(tp), decisions(t32)))
         draws.append((op, lp))
+        fwd_draws.append((tuple(o.detach() for o in op), _detached(tp)))
     gd32 = [render_grads(op, lp, gc, gm, gd, keep) for op, lp in draws]
     if not bool(keep.all()):                     # a ray dropped by a later draw: the first two again without it
         g64, g32 = render_grads(o64, l64, gc, gm, gd, keep), render_grads(o32, l32, gc, gm, gd, keep)
     return dict(out64=tuple(o.detach() for o in o64), out32=tuple(o.detach() for o in o32), g64=g64, g32=g32, draws=gd32,
-                keep=keep, taps32=t32)
+                keep=keep, taps64=_detached(t64), taps32=t32, fwd_draws=fwd_draws)
 
 
-def perturb(t, seed):
-    """t with every element moved by -1, 0 or +1 ulp (at random; float32)"""
+def _detached(taps):
+    return {k: (v.detach() if torch.is_tensor(v) else v) for k, v in taps.items()}
+
+
+def perturb(t, seed, ulps=1):
+    """t with every element moved by -ulps, 0 or +ulps ulp (at random; float32)"""
     g = torch.Generator().manual_seed(seed)
-    return t * (1 + torch.randint(-1, 2, t.shape, generator=g).float() * 2 ** -23)
+    return t * (1 + torch.randint(-1, 2, t.shape, generator=g).float() * (ulps * 2 ** -23))
 
 
-def perturbed_scene(sc, i):
-    """a shallow copy of the Scene whose tri-plane, MLP parameters and z_rend are moved by up to one ulp"""
+def perturbed_scene(sc, i, ulps=1):
+    """a shallow copy of the Scene whose tri-plane, MLP parameters and z_rend are moved by up to `ulps` ulp"""
     import copy
     c = copy.copy(sc)
     c.raw = dict(sc.raw)
-    c.raw["tri_plane"] = perturb(sc.raw["tri_plane"], 3000 + i)
-    c.raw["mlp"] = {k: perturb(v, 4000 + 97 * i + j) for j, (k, v) in enumerate(sorted(sc.raw["mlp"].items()))}
-    c.raw["z_rend"] = perturb(sc.raw["z_rend"], 5000 + i)
+    c.raw["tri_plane"] = perturb(sc.raw["tri_plane"], 3000 + i, ulps)
+    c.raw["mlp"] = {k: perturb(v, 4000 + 97 * i + j, ulps) for j, (k, v) in enumerate(sorted(sc.raw["mlp"].items()))}
+    c.raw["z_rend"] = perturb(sc.raw["z_rend"], 5000 + i, ulps)
     return c
 
 

@@ -7,27 +7,22 @@ do not: both render_bwd_kernel instantiations over ragged fine counts (Nf 2 .. 1
 render_scale != 1, rays that hit no cube, per-image tri-planes under group_frames, a forced drop_invalid_rays, non-square and
 2 x 2 planes, the density modes, a tri-plane shared by three images and the channel-last feature gradient. enarf_query_bwd runs on points placed in
 canonical space (long runs of samples on one texel, texel centres and edges, the plane border), enarf_weight_grad and
-enarf_prepare_bwd on synthetic inputs."""
+enarf_prepare_bwd on synthetic inputs. The forward launch of every render case is held entry by entry as well
+(tests/fwd_referee.py), on the same referee's float64 and fp32 renders."""
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+import fwd_referee as FR
 import grad_referee as R
 from _helpers import DeviceScene, Scene, assert_close, bits_of
+from fwd_cases import query_points as _query_points, rays as _rays
 from oracle import enarf_oracle as O
 
 pytestmark = pytest.mark.gpu
 
 ATOMIC_TOL = 2e-5       # of max |gradient|: re-ordered float sums (atomics, split-K partials); tests/test_gpu_backward_sizes.py
-
-
-def _rays(S, n_body, n_miss, seed):
-    """n_body ray ids through the middle rows of an S x S frame (most hit a cube) and n_miss from its first row (none do)"""
-    g = torch.Generator().manual_seed(seed)
-    body = S * (S // 2 - 2) + torch.randperm(4 * S, generator=g)[:n_body]
-    miss = torch.arange(n_miss)
-    return torch.cat([miss, body.sort().values])
 
 
 def _kernel_grads(ds, coord_d, Nf, bins_d, gc, gm, gd, **kw):
@@ -76,9 +71,9 @@ def _case(sc, ids, Nc, Nf, render_scale=1.0, seed=7, modes=None, bwd_kw=None, wh
         assert np.allclose(dk, do, rtol=1e-6, atol=0), f"{what}: {k} differs from the oracle's"
     keep = ref["keep"]
     assert float(keep.float().mean()) > 0.9, f"{what}: float64 and fp32 disagree on {int((~keep).sum())} of {keep.numel()} rays"
-    # forward values against float64
-    assert_close(fwd.color.cpu(), ref["out64"][0].float(), f"{what}: colour vs float64")
-    assert_close(fwd.mask.cpu(), ref["out64"][1].float(), f"{what}: mask vs float64")
+    # forward values against float64: every sample and ray output entry by entry (tests/fwd_referee.py), on the referee's draws
+    fwd_ratios = FR.check_forward(FR.kernel_tensors(fwd), FR.from_grad_referee(ref), f"{what}: forward")
+    print(f"{what}: forward, worst error / bound per tensor: {FR.fmt(fwd_ratios)}")
     assert float(ref["out64"][1].max()) > 0.3, what
     kd = keep.float()
     ours = _kernel_grads(ds, coord.to(ds.dev), Nf, bins.to(ds.dev), gc * kd[:, None], gm * kd, gd * kd,
@@ -209,50 +204,6 @@ def test_render_bwd_drop_invalid_rays_forced():
 
 
 # ------------------------------------------------------------------------------------------ query_bwd on placed points
-def _place(sc, b, k, canon):
-    """canonical points (3, M) float64 of part k of image b -> camera points of the scaled space (3, M) float32"""
-    Rc, tc = sc.cpose[k, :3, :3].double(), sc.cpose[k, :3, 3].double()
-    pose = sc.pose_scaled[b, k].double()
-    s = sc.scale[b, k].double()
-    local = (Rc.T @ (canon - tc[:, None])) / s
-    return (pose[:3, :3] @ local + pose[:3, 3:4]).float()
-
-
-def _query_points(sc, b, H, W):
-    """(3, N) points of image b, N % 64 != 0, placed in the canonical cube of part 5 (half-size = its scale s, around its
-    canonical origin tc; the points stay within s / 2 of tc so that every one is valid): runs of 16 samples along each
-    plane axis inside one texel and across one texel edge, texel centres and texel edges in both plane coordinates, the
-    valid region's faces, and points far from every part."""
-    k = 5
-    tc = sc.cpose[k, :3, 3].double()
-    lim = 0.5 * float(sc.scale[b, k])
-    cx = lambda i, n: (2 * i + 1) / n - 1                     # texel centre i of n
-    ex = lambda i, n: (2 * i + 2) / n - 1                     # edge between texels i and i + 1
-    near = lambda v, n: int(((v + 1) * n - 1) / 2)            # the texel under coordinate v
-    pts = []
-    for axis in range(3):
-        for at in (ex, cx):                                   # 16 samples with one bilinear footprint / with two
-            c = tc[:, None].repeat(1, 16)
-            u, v = axis, (axis + 1) % 3
-            c[u] = at(near(float(tc[u]), W), W) + torch.linspace(-0.6 / W, 0.6 / W, 16, dtype=torch.float64)
-            c[v] = cx(near(float(tc[v]), H), H)
-            pts.append(_place(sc, b, k, c))
-    g = torch.Generator().manual_seed(4)
-    off = lambda n: torch.randint(-int(lim * n / 2) + 1, int(lim * n / 2) - 1, (40,), generator=g)
-    for f in (cx, ex):                                        # centres and edges in every coordinate
-        c = torch.stack([f(near(float(tc[d]), W if d != 1 else H) + off(W if d != 1 else H), W if d != 1 else H).double()
-                         for d in range(3)])
-        pts.append(_place(sc, b, k, c))
-    c = tc[:, None].repeat(1, 24)                             # close to the faces of the region
-    c[0] += torch.tensor([0.999 * lim, -0.999 * lim, 0.5 * lim, -0.5 * lim] * 6, dtype=torch.float64)
-    c[1] += torch.linspace(-0.9 * lim, 0.9 * lim, 24, dtype=torch.float64)
-    pts.append(_place(sc, b, k, c))
-    pts.append(torch.full((3, 7), 40.0))
-    out = torch.cat(pts, dim=1)
-    assert out.shape[1] % 64 != 0
-    return out
-
-
 @pytest.mark.parametrize("modes", [{}, dict(multiply_density_with_weight=True, clamp_mask=True)])
 def test_query_bwd_placed_points_vs_float64(modes):
     from enarf_gan_amd import ops

@@ -39,6 +39,58 @@ __device__ __forceinline__ void stage_common(float *lds, QueryCtx &S, float *&sc
     S.canon = l_canon;
 }
 
+// The same staging by NT threads with every global load of a thread in flight before its first LDS store. The loops above
+// wait for each load before they issue the next (their trip counts are run-time values): seven round trips for the MLP
+// section, five more for biases and frames - a third of render_kernel's start-up (DESIGN.md 3.1 "start-up"). Loads past the
+// end of a section are clamped to its last element, not branched around, and their stores skipped.
+template <int MODE, int NT>
+__device__ __forceinline__ void stage_common_batched(float *lds, QueryCtx &S, float *&scratch, const void *pack_b,
+                                                     const float *parts_b, const float *canon_pose, int P, int tid) {
+    float *l_mlp = lds;
+    float *l_bias = l_mlp + lds_mlp_floats<MODE>();
+    float *l_parts = l_bias + 144;
+    float *l_canon = l_parts + P * kLdsPartStride;
+    scratch = l_canon + P * kLdsCanonStride;
+    const float *pf = reinterpret_cast<const float *>(pack_b);
+    const f32x4 *src4 = (MODE == ENARF_MLP_F32) ? reinterpret_cast<const f32x4 *>(pf)
+                        : (MODE == ENARF_MLP_F16X3) ? reinterpret_cast<const f32x4 *>(pf + PK_F32_FLOATS + PKH_SHORTS / 2)
+                                                    : reinterpret_cast<const f32x4 *>(pf + PK_F32_FLOATS);
+    f32x4 *dst4 = reinterpret_cast<f32x4 *>(l_mlp);
+    constexpr int N4 = lds_mlp_floats<MODE>() / 4, KM = (N4 + NT - 1) / NT;
+    constexpr int KP = (ENARF_MAX_PARTS * kPartStride + NT - 1) / NT, KC = (ENARF_MAX_PARTS * 12 + NT - 1) / NT;
+    static_assert(NT >= 144, "one bias per thread");
+    const int np = P * kPartStride, nc = P * 12;
+    f32x4 rm[KM];
+    float rp[KP], rc[KC];
+#pragma unroll
+    for (int k = 0; k < KM; ++k) rm[k] = src4[min(tid + k * NT, N4 - 1)];
+    const float rb = pf[PK_B1 + min(tid, 143)];
+#pragma unroll
+    for (int k = 0; k < KP; ++k) rp[k] = parts_b[min(tid + k * NT, np - 1)];
+#pragma unroll
+    for (int k = 0; k < KC; ++k) {   // (P,4,4) -> Rc row-major 9 + tc 3, as stage_frames
+        const int i = min(tid + k * NT, nc - 1), j = i / 12, e = i % 12;
+        rc[k] = canon_pose[j * 16 + ((e < 9) ? (e / 3) * 4 + (e % 3) : (e - 9) * 4 + 3)];
+    }
+#pragma unroll
+    for (int k = 0; k < KM; ++k)
+        if (tid + k * NT < N4) dst4[tid + k * NT] = rm[k];
+    if (tid < 144) l_bias[tid] = rb;
+#pragma unroll
+    for (int k = 0; k < KP; ++k) {
+        const int i = tid + k * NT;
+        if (i < np) l_parts[(i / kPartStride) * kLdsPartStride + (i % kPartStride)] = rp[k];
+    }
+#pragma unroll
+    for (int k = 0; k < KC; ++k)
+        if (tid + k * NT < nc) l_canon[tid + k * NT] = rc[k];
+    S.mlp = l_mlp;
+    S.mlp_h = reinterpret_cast<const short *>(l_mlp);
+    S.bias = l_bias;
+    S.parts = l_parts;
+    S.canon = l_canon;
+}
+
 // head: tanh colour, MyReLU * 10 density, density *= any_valid   (triplane_nerf.py:44-47, narf.py:271-274, :204)
 __device__ __forceinline__ float density_head(float sigma_act, uint32_t bits, float wmax, int mult_w, int P) {
     float d = fmaxf(sigma_act, 0.0f);

@@ -92,13 +92,17 @@ __device__ __forceinline__ float part_centre_z(const enarf_prepare_args &a, int 
 
 constexpr int kPrepareSmemFloats = 2 * kHid + kHid * kHid;     // s_style, s_inv, s_w
 
-// block (layer, b): one layer of image b's MLP pack; the layer-0 block also writes the part frames
-__device__ __forceinline__ void prepare_block(const enarf_prepare_args &a, int layer, int b, int tid, float *smem) {
+// block (layer, b): output rows [row0, row0 + nrows) of one layer of image b's MLP pack - the whole layer, or a slice of it:
+// a row's demodulation needs that row only, so slices of a layer are independent blocks that each redo the layer's short
+// style product. The block with row 0 of layer 0 also writes the part frames; layer 2 (4 rows and the zero rows of its
+// operand tiles) is not sliced.
+__device__ __forceinline__ void prepare_block(const enarf_prepare_args &a, int layer, int b, int tid, float *smem, int row0 = 0,
+                                              int nrows = kHid) {
     const int J = a.num_joints;
     const int P = (a.origin_location == ENARF_ORIGIN_CENTER_HEAD) ? J : J - 1;
     float *s_style = smem, *s_inv = smem + kHid, *s_w = smem + 2 * kHid;
 
-    if (layer == 0 && a.parts && tid < P) {
+    if (layer == 0 && row0 == 0 && a.parts && tid < P) {
         float fr[16];
         compute_part_frame(a, b, tid, fr);
         float *out = a.parts + ((size_t)b * P + tid) * kPartStride;
@@ -111,6 +115,7 @@ __device__ __forceinline__ void prepare_block(const enarf_prepare_args &a, int l
     short *ph = reinterpret_cast<short *>(pf + PK_F32_FLOATS);
     const int cin = (layer == 0) ? kFeat : kHid;
     const int cout = (layer == 2) ? 4 : kHid;
+    const int e0 = row0 * cin, ne = ((row0 + nrows < cout ? row0 + nrows : cout) - row0) * cin;      // this block's elements
     if (layer == 2) {   // rows 4..15 of the last layer's 16-row operand tiles are zero; layers 0/1 write every element
         for (int i = tid; i < 16 * 64; i += 256) pf[PK_W3 + i] = 0.0f;
         for (int i = tid; i < 16; i += 256) pf[PK_B3 + i] = 0.0f;
@@ -123,7 +128,7 @@ __device__ __forceinline__ void prepare_block(const enarf_prepare_args &a, int l
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
         const int e = tid + 256 * i;
-        cw[i] = (e < cout * cin) ? a.conv_weight[layer][e] : 0.0f;
+        cw[i] = (e < ne) ? a.conv_weight[layer][e0 + e] : 0.0f;
     }
     if (tid < cin) {   // EqualLinear: z @ (Wm * scale)^T + b_mod
         const float *wm = a.mod_weight[layer] + (size_t)tid * a.style_dim;
@@ -136,18 +141,35 @@ __device__ __forceinline__ void prepare_block(const enarf_prepare_args &a, int l
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
         const int e = tid + 256 * i;
-        if (e < cout * cin) s_w[e] = (cscale * cw[i]) * s_style[e % cin];
+        if (e < ne) s_w[e0 + e] = (cscale * cw[i]) * s_style[e % cin];
     }
     __syncthreads();
-    if (tid < cout) {   // F.normalize(dim=-1, eps=1e-12)
+    if (tid * cin < ne) {   // F.normalize(dim=-1, eps=1e-12) of row row0 + tid
+        const int o = row0 + tid;
         float ss = 0.0f;
-        for (int c = 0; c < cin; ++c) ss += s_w[tid * cin + c] * s_w[tid * cin + c];
-        s_inv[tid] = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
+        for (int c = 0; c < cin; ++c) ss += s_w[o * cin + c] * s_w[o * cin + c];
+        s_inv[o] = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
         const int boff = (layer == 0) ? PK_B1 : (layer == 1) ? PK_B2 : PK_B3;
-        pf[boff + tid] = a.bias[layer][tid];
+        pf[boff + o] = a.bias[layer][o];
     }
     __syncthreads();
-    for (int e = tid; e < cout * cin; e += 256) pack_weight_row(pf, ph, layer, e / cin, e % cin, s_w[e] * s_inv[e / cin]);
+    for (int e = e0 + tid; e < e0 + ne; e += 256) pack_weight_row(pf, ph, layer, e / cin, e % cin, s_w[e] * s_inv[e / cin]);
+}
+
+// The prepare role of the fused pre-march launch slices layers 0 and 1 into blocks of 512 weights (two per thread): one
+// block per layer spent most of its life issuing its 4 096 weights' scattered stores into the operand-ordered pack (five per
+// weight, 64 cache lines per wave instruction) from ONE CU, and was the last block of the launch to finish.
+constexpr int kPrepSlices0 = kFeat * kHid / 512, kPrepSlices1 = kHid * kHid / 512;
+constexpr int kPrepBlocksPerImage = kPrepSlices0 + kPrepSlices1 + 1;
+static_assert(kHid % kPrepSlices0 == 0 && kHid % kPrepSlices1 == 0, "whole rows per slice");
+__device__ __forceinline__ void prepare_role_block(const enarf_prepare_args &a, int id, int tid, float *smem) {
+    const int b = id / kPrepBlocksPerImage, s = id % kPrepBlocksPerImage;
+    // ONE call with the layer as a run-time value, as in prepare_kernel: a call per layer lets the compiler fold the layer's
+    // 1 / sqrt(cin) on the host, which need not round as the device's does - and the two entries promise the same bits
+    const int layer = (s >= kPrepSlices0 ? 1 : 0) + (s >= kPrepSlices0 + kPrepSlices1 ? 1 : 0);
+    const int slice = s - (layer == 0 ? 0 : layer == 1 ? kPrepSlices0 : kPrepSlices0 + kPrepSlices1);
+    const int nrows = layer == 0 ? kHid / kPrepSlices0 : layer == 1 ? kHid / kPrepSlices1 : kHid;
+    prepare_block(a, layer, b, tid, smem, slice * nrows, nrows);
 }
 
 __global__ __launch_bounds__(256) void prepare_kernel(const PrepareParams prm) {   // grid = (3, B)
@@ -634,7 +656,7 @@ __global__ __launch_bounds__(256) void pre_march_kernel(const PreParams q) {
     // long-latency roles first (few blocks, serial chains), the bandwidth-bound re-layout blocks fill in behind them
     if (id < q.n_prep) {
         if (id == 0) ws_clear_other_header(q.rend.workspace, q.rend.ws_epoch, tid);
-        prepare_block(q.prep, id % 3, id / 3, tid, smem);
+        prepare_role_block(q.prep, id, tid, smem);
         return;
     }
     id -= q.n_prep;
@@ -698,8 +720,9 @@ __global__ __launch_bounds__(256, kRenderWavesPerSimd) void render_kernel(const 
     int cur = rq.get(0);
     if (cur < 0) return;                      // uniform: every queue is already drained
     int b = (int)((uint32_t)cur / (uint32_t)n);
-    stage_common<MODE>(lds, S, scratch, reinterpret_cast<const char *>(a.mlp_pack) + (size_t)b * kPackBytes,
-                       a.parts + (size_t)b * P * kPartStride, a.canonical_pose, P, tid, 256);
+    // every load of the image context in flight at once: the plain staging loop waits for each before it issues the next
+    stage_common_batched<MODE, 256>(lds, S, scratch, reinterpret_cast<const char *>(a.mlp_pack) + (size_t)b * kPackBytes,
+                                    a.parts + (size_t)b * P * kPartStride, a.canonical_pose, P, tid);
     S.feat = a.feat_cl + (size_t)b * a.feat_batch_stride;
     S.mask = a.mask_planes + (size_t)b * a.mask_batch_stride;
     S.H = a.H; S.W = a.W; S.P = P; S.mult_w = a.multiply_density_with_weight ? (a.uniform_part_weight ? 2 : 1) : 0;
@@ -1169,7 +1192,7 @@ static int launch_pre_march(const enarf_prepare_args &p, const float *tri_nchw, 
     q.prep = p; q.rend = r; q.tri = tri_nchw; q.feat_cl = feat_cl; q.tri_B = tri_B; q.ch_total = channels_total;
     q.H = r.H; q.W = r.W;
     q.n_pack = tri_nchw ? ((r.W + 63) / 64) * r.H * tri_B * 3 : 0;
-    q.n_prep = 3 * p.B;
+    q.n_prep = kPrepBlocksPerImage * p.B;
     q.bpi = ws_setup_blocks(r.n);
     const long long blocks = (long long)q.n_pack + q.n_prep + (long long)q.bpi * r.B;
     if (blocks > 0x7FFFFFFFll) return host::fail(ENARF_ERR_UNSUPPORTED, "enarf_render_step_fwd: too many blocks");

@@ -312,3 +312,75 @@ def render_posable(model, image_coord: torch.Tensor, pose_to_camera: torch.Tenso
     model.buffers_tensors.update(bins=t["bins"], fine_depth=fine_depth[:, None], fine_weights=w.detach()[:, None],
                                  fine_points=fine_points)
     return rc, rm, rd
+
+
+def _march_taps(model, image_coord, inv_intrinsics, parts, tri, feat_cl, pack, Nc, Nf, render_scale, seed, flags):
+    """One renderer batch on the rays of one camera, with its taps: (fine_depth (B, n, Nf), fine_density (B, n, Nf),
+    fine_color (B, 3, n, Nf), ray_validity (B, n) uint8, mask (B, n)) of the B images of `parts`."""
+    B, n = parts.shape[0], image_coord.shape[-1]
+    coord = image_coord.reshape(1, 3, n).expand(B, -1, -1)
+    Ki = inv_intrinsics.reshape(-1, 3, 3)[:1].expand(B, -1, -1)
+    out = ops.render_fwd(coord, Ki, parts, model.canonical_pose, tri, feat_cl, pack, Nc, Nf, render_scale=render_scale,
+                         seed=seed, mlp_mode=model.mlp_mode, debug=True, **flags)
+    t = out.taps
+    return out.fine_depth[:, 0], t["fine_density"], t["fine_color"], t["ray_validity"], out.mask
+
+
+def composite_marches(model, marches, axis: int, render_scale: float = 1, threshold: float = 0.5):
+    """The taps of several `_march_taps` batches to one image per frame, in one ops.scene_composite launch. axis = 0: the
+    batches are groups of avatars of one frame, joined along the avatars; axis = 1: batch k holds avatar k in every
+    frame. Returns (colour (F, 3, n), mask (F, n), disparity (F, n)) and leaves instance_mass (F, K, n), instance (F, n),
+    skipped (F, n) and avatar_masks (F, K, n), the avatars' own masks, in model.buffers_tensors. One batch of one frame is
+    passed on as it is, without a copy."""
+    if axis == 0:
+        join = (lambda ts: ts[0][None]) if len(marches) == 1 else (lambda ts: torch.cat(ts, dim=0)[None])
+    else:
+        join = lambda ts: torch.stack(ts, dim=1)
+    depth, density, color, valid, masks = (join([m[i] for m in marches]) for i in range(5))
+    res = ops.scene_composite(depth, density, color, valid, render_scale=render_scale, threshold=threshold)
+    if not hasattr(model, "buffers_tensors"):
+        model.buffers_tensors = {}
+    model.buffers_tensors.update(instance_mass=res.instance_mass, instance=res.instance, skipped=res.skipped,
+                                 avatar_masks=masks)
+    return res.color, res.mask, res.disparity
+
+
+def render_scene(model, image_coord: torch.Tensor, pose_to_camera: torch.Tensor, inv_intrinsics: torch.Tensor,
+                 render_scale: float = 1, Nc: int = 64, Nf: int = 128, model_input: Dict = {},
+                 avatars_per_batch: Optional[int] = None, seed: Optional[int] = None, threshold: float = 0.5,
+                 _parts: Optional[torch.Tensor] = None, _pack: Optional[torch.Tensor] = None):
+    """K avatars in front of one camera: image_coord (1, 1, 3, n) or (1, 3, n), pose_to_camera (K, P, 4, 4) part frames,
+    one inv_intrinsics ((3, 3) or (1, 3, 3)); model_input is batched over the avatars (z, z_rend, bone_length and, when
+    given, tri_plane_feature of K entries) -> colour (1, 3, n), mask (1, n), disparity (1, n) of the scene.
+
+    The avatars are marched on the same rays by the fused march with its taps (ops.render_fwd(debug=True)) under no_grad
+    and on the same `seed`, avatars_per_batch at a time (default: all K in one renderer batch; a batch shares its near / far
+    planes and numbers its rays batch-wide, so with avatars_per_batch=1 every avatar's samples are exactly those of its
+    own render() call). One ops.scene_composite launch then integrates the sum of the K media over the merged samples
+    of every ray (include/enarf_scene.h), where pasting the K images over each other by mask is wrong: bodies that
+    interleave in depth, soft silhouettes. Each avatar keeps its own samples; no avatar is queried at another's.
+    model.buffers_tensors gets instance_mass (1, K, n), the share of the mask each avatar carries, instance (1, n) int32,
+    the avatar of the largest share where mask >= threshold (else -1), skipped (1, n) int32, a bit for every avatar whose
+    samples were unusable on the ray, and avatar_masks (1, K, n), the avatars' own masks. No gradient flows."""
+    assert pose_to_camera.shape[1] == model.num_bone
+    K = pose_to_camera.shape[0]
+    per = K if avatars_per_batch is None else int(avatars_per_batch)
+    if per < 1:
+        raise ValueError(f"render_scene: avatars_per_batch {avatars_per_batch} < 1")
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    if not hasattr(model, "buffers_tensors"):
+        model.buffers_tensors = {}
+    flags = model.kernel_flags()
+    with torch.no_grad():
+        parts = _parts_from_part_poses(model, pose_to_camera, model_input["bone_length"]) if _parts is None else _parts
+        marches = []
+        for a in range(0, K, per):
+            b = min(a + per, K)
+            mi = {k: (v[a:b] if isinstance(v, torch.Tensor) and v.dim() > 0 and v.shape[0] == K else v)
+                  for k, v in model_input.items()}
+            tri, feat_cl = model._tri_plane_pair(mi)
+            pack = model._mlp_pack(mi["z_rend"]) if _pack is None else _pack[a:b]
+            marches.append(_march_taps(model, image_coord, inv_intrinsics, parts[a:b], tri, feat_cl, pack, Nc, Nf,
+                                       render_scale, seed, flags))
+        return composite_marches(model, marches, 0, render_scale, threshold)

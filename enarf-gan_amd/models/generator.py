@@ -388,6 +388,124 @@ class TriNARFGenerator(_RendererShell):
                 ops.compose_frames(color, alpha, backdrop, out=(frames[a:b], masks[a:b]))
         return frames, masks, poses
 
+    def _scene_backdrop(self, background, z_bg, z_render, device):
+        """The one background of a scene: "first" runs the background network on the first avatar's latents (-1 on a
+        generator with a black background), a (1, 3, S, S) tensor is taken as it is, a number is a flat colour (-1: black)."""
+        S = self.size
+        if isinstance(background, str):
+            if background != "first":
+                raise ValueError(f"render_scene: background {background!r} is neither 'first', a (1, 3, {S}, {S}) tensor nor a number")
+            return self._background(None if z_bg is None else z_bg[:1], z_render[:1], False)
+        if isinstance(background, torch.Tensor):
+            if tuple(background.shape) != (1, 3, S, S):
+                raise ValueError(f"render_scene: a background image is (1, 3, {S}, {S}), got {tuple(background.shape)}")
+            return background.to(device=device, dtype=torch.float32)
+        try:
+            return float(background)
+        except (TypeError, ValueError):
+            raise ValueError(f"render_scene: background {background!r} is neither 'first', a (1, 3, {S}, {S}) tensor nor a "
+                             "number") from None
+
+    @staticmethod
+    def _instance_image(instance, K):
+        """(F, S, S) int32 avatar indices -> (F, 3, S, S) fp32 in the colours of semantic_palette(K), white where no avatar
+        owns the pixel"""
+        from ..libraries.NeRF.rendering import semantic_palette
+        palette = semantic_palette(K, instance.device)
+        rgb = torch.where(instance[..., None] >= 0, palette[instance.clamp(min=0).long()], palette.new_ones(()))
+        return rgb.permute(0, 3, 1, 2).contiguous()
+
+    @torch.no_grad()
+    def render_scene(self, pose_to_camera, bone_length, z, inv_intrinsics, truncation_psi=1, background="first",
+                     return_instances=False, avatars_per_batch=None, return_bg=False, threshold=0.5, seed=None):
+        """K identities in K poses in front of one camera, in one image: pose_to_camera (K, J, 4, 4), bone_length and z of
+        batch K, one inv_intrinsics -> (image (1, 3, S, S), mask (1, S, S)); with return_instances also (instance map
+        (1, S, S) int32 - the avatar that carries the largest share of the pixel's mask, -1 where the mask is below
+        `threshold` -, its colour image (1, 3, S, S) in semantic_palette(K), white without an avatar). The avatars are
+        marched on the same rays and composed by rendering.render_scene (one ops.scene_composite launch: depth-correct
+        where bodies interleave, avatars_per_batch as there); image = colour + (1 - mask) background as forward()
+        composes it, the background as _scene_backdrop takes it ("first": the background network on the first avatar's
+        latents). return_bg returns (colour, mask, background) uncomposed, as forward(return_bg=True). The shares are
+        left in self.nerf.buffers_tensors (instance_mass, skipped, avatar_masks). All on the device, no host
+        synchronisation inside (a `seed` of None draws one from torch's CPU generator, as render() does)."""
+        from .. import ops
+        from ..libraries.NeRF.rendering import render_scene
+        nerf, S, K = self.nerf, self.size, pose_to_camera.shape[0]
+        if not (z.shape[0] == K and bone_length.shape[0] == K):
+            raise AssertionError(f"render_scene takes z and bone_length of batch K = {K}, one entry an avatar")
+        dev = pose_to_camera.device
+        _, pixels = self.ray_sampler(S, S, 1, device=dev)
+        z_nerf, z_render, z_bg = self._latent_parts(z)
+        K_inv = torch.as_tensor(inv_intrinsics).float().to(dev)
+        parts, pack = ops.prepare(pose_to_camera, bone_length, nerf.canonical_bone_length, z_render, nerf.mlp.as_dict(),
+                                  nerf.parent_id, nerf.origin_location, nerf.coordinate_scale)
+        model_input = {"z": z_nerf, "z_rend": z_render, "bone_length": bone_length, "truncation_psi": truncation_psi}
+        color, mask, _ = render_scene(nerf, pixels, pose_to_camera.new_empty(K, nerf.num_bone, 4, 4), K_inv,
+                                      model_input=model_input, avatars_per_batch=avatars_per_batch, seed=seed,
+                                      threshold=threshold, _parts=parts, _pack=pack, **self._samples)
+        person, alpha = color.reshape(1, 3, S, S), mask.reshape(1, S, S)
+        backdrop = self._scene_backdrop(background, z_bg, z_render, dev)
+        if return_bg:
+            return person, alpha, backdrop
+        image = person + (1 - alpha[:, None]) * backdrop
+        if not return_instances:
+            return image, alpha
+        instance = nerf.buffers_tensors["instance"].reshape(1, S, S)
+        return image, alpha, instance, self._instance_image(instance, K)
+
+    def render_scene_animation(self, key_poses, bone_length, intrinsics, z, num=100, loop=True, orbit=None, truncation_psi=0.4,
+                               frames_per_batch=8, background="first", threshold=0.5):
+        """K identities in motion in front of one camera, on the device from end to end: (frames (num, S, S, 3) uint8,
+        masks (num, S, S) uint8, instances (num, S, S) int32, poses (K, num, J, 4, 4) in key_poses' dtype), all device
+        tensors, with no host synchronisation inside.
+
+        key_poses (K, Kp, J, 4, 4), or a list of K (Kp, J, 4, 4) tensors, joint-to-camera key poses on the device; z and
+        bone_length of batch K; intrinsics (3, 3) or (1, 3, 3); num, loop and orbit as in ops.interpolate_pose, one
+        launch an avatar. The tri-plane of every avatar and the background are computed once. The frames are marched
+        frames_per_batch at a time, avatar by avatar on its own tri-plane (a renderer batch is one avatar in the
+        chunk's frames, every avatar on the chunk's one seed), and each chunk takes one ops.scene_composite launch and one
+        ops.compose_frames launch. frames_per_batch=1 gives the bytes of render_scene(avatars_per_batch=1) on each
+        frame's poses."""
+        from .. import ops
+        from ..libraries.NeRF.rendering import _march_taps, composite_marches
+        K = len(key_poses)
+        if not (z.shape[0] == K and bone_length.shape[0] == K):
+            raise AssertionError(f"render_scene_animation takes z and bone_length of batch K = {K}, one entry an avatar")
+        per = int(frames_per_batch)
+        if per < 1:
+            raise ValueError(f"render_scene_animation: frames_per_batch {frames_per_batch} < 1")
+        nerf, S = self.nerf, self.size
+        with torch.no_grad():
+            both = [ops.interpolate_pose(key_poses[k], nerf.parent_id, num, loop, orbit, return_f32=True) for k in range(K)]
+            poses = torch.stack([p for p, _ in both])
+            dev, n_frames = poses.device, poses.shape[1]
+            z_nerf, z_render, z_bg = self._latent_parts(z)
+            tri = [nerf.compute_tri_plane_feature(z_nerf[k:k + 1], bone_length[k:k + 1], truncation_psi).detach().contiguous()
+                   for k in range(K)]
+            feat = [ops.triplane_pack(t) for t in tri]
+            backdrop = self._scene_backdrop(background, z_bg, z_render, dev)
+            K_inv = torch.linalg.inv_ex(torch.as_tensor(intrinsics).float().to(dev).reshape(-1, 3, 3)[:1]).inverse
+            _, pixels = self.ray_sampler(S, S, 1, device=dev)
+            frames = torch.empty((n_frames, S, S, 3), dtype=torch.uint8, device=dev)
+            masks = torch.empty((n_frames, S, S), dtype=torch.uint8, device=dev)
+            instances = torch.empty((n_frames, S, S), dtype=torch.int32, device=dev)
+            mlp, flags = nerf.mlp.as_dict(), nerf.kernel_flags()
+            for a in range(0, n_frames, per):
+                b = min(a + per, n_frames)
+                c = b - a
+                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+                marches = []
+                for k in range(K):
+                    bl, z_rend = bone_length[k:k + 1].expand(c, -1, -1), z_render[k:k + 1].expand(c, -1)
+                    parts, pack = ops.prepare(both[k][1][a:b], bl, nerf.canonical_bone_length, z_rend, mlp, nerf.parent_id,
+                                              nerf.origin_location, nerf.coordinate_scale)
+                    marches.append(_march_taps(nerf, pixels, K_inv, parts, tri[k], feat[k], pack, self._samples["Nc"],
+                                               self._samples["Nf"], 1, seed, flags))
+                color, alpha, _ = composite_marches(nerf, marches, 1, 1, threshold)
+                ops.compose_frames(color, alpha, backdrop, out=(frames[a:b], masks[a:b]))
+                instances[a:b] = nerf.buffers_tensors["instance"].reshape(c, S, S)
+        return frames, masks, instances, poses
+
 
 class DSONARFGenerator(_RendererShell):
     def __init__(self, config, size, num_bone=1, parent_id=None, num_bone_param=None):

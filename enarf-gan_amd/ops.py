@@ -1015,3 +1015,28 @@ def geometry_buffers(disparity: torch.Tensor, mask: torch.Tensor, inv_intrinsics
     return _geom_lib.geometry_buffers(disparity, mask, inv_intrinsics, size, origin, step, depth_scale, mask_threshold, edge,
                                       normalise, shade, near, far, background, want, out)
 
+
+
+# ------------------------------------------------------------------------------------------------- multi-avatar scenes
+from ._scene_lib import SceneComposite  # noqa: E402,F401  (scene_composite's result)
+
+
+def scene_composite(depth: torch.Tensor, density: torch.Tensor, color: torch.Tensor, valid: Optional[torch.Tensor] = None, *,
+                    render_scale=1.0, threshold=0.5,
+                    want=("color", "mask", "disparity", "instance_mass", "instance", "skipped"), out=None):
+    """K avatars marched on the same n rays to one image, in one launch of libenarf_scene.so: the namedtuple SceneComposite
+    (color (F, 3, n), mask (F, n), disparity (F, n), instance_mass (F, K, n) fp32, instance (F, n) and skipped (F, n) int32,
+    and the merged samples t, source, weight (F, n, K Nf)); a field not named in `want` is None and is not written. depth
+    and density are (F, K, n, Nf), color (F, K, 3, n, Nf), valid (F, K, n) uint8 or None - the fine_depth, fine_density and
+    fine_color taps and the ray_validity of render_fwd(debug=True) on a batch of F K images, read in place; without the
+    frame axis (K, n, Nf) is one frame and the outputs lose it too. Every avatar is the medium of the march's own
+    quadrature on the running maximum of its depths; the scene is the sum of the media, integrated over the merged
+    breakpoints (include/enarf_scene.h): mask = 1 - exp(-sum tau), instance_mass sums to the mask over the avatars,
+    instance is the avatar of the largest share where mask >= threshold, else -1. An avatar takes no part on a ray where
+    its validity byte is 0, or - bit k of `skipped` is then set - where a value is not finite, a depth <= 0 or a density
+    < 0. `out` maps names of `want` to contiguous tensors to write into. Computed in fp64 from the fp32 inputs,
+    bit-identical from run to run, nothing synchronises, F n = 0 launches nothing. No gradient: inputs that require one
+    raise NotImplementedError, as do K outside [1, 8], Nf outside [2, 128] and K Nf > 512; ValueError for shapes or dtypes
+    it does not take."""
+    from . import _scene_lib
+    return _scene_lib.scene_composite(depth, density, color, valid, render_scale, threshold, want, out)

@@ -317,8 +317,12 @@ def query(points: torch.Tensor, pose_scaled: torch.Tensor, scale: torch.Tensor,
         density = density * 10
     density = density * valid.any(dim=1, keepdim=True)
     if return_taps:
+        # the density before its ReLU, through the same factors (relu(signed_density) == density): what a bound on the
+        # density's error is measured on where the ReLU hides it (tests/fwd_referee.py)
+        gain = 10 * w.max(dim=1, keepdim=True)[0] if multiply_density_with_weight else 10
+        signed = h[:, 3:] * gain * valid.any(dim=1, keepdim=True)
         return density, color, valid, {"local": local, "canonical": canonical, "weight": w,
-                                       "feature": feat, "mlp_out": h}
+                                       "feature": feat, "mlp_out": h, "signed_density": signed}
     return density, color, valid
 
 
@@ -473,16 +477,16 @@ def render(image_coord: torch.Tensor, pose_parts: torch.Tensor, bone_length_part
 
     cdepth, cpts, start, end = coarse_points(rd, dmin, dmax, Nc)
     qkw = dict(multiply_density_with_weight=multiply_density_with_weight, clamp_mask=clamp_mask, no_selector=no_selector)
-    cden, _, cvalid = query(cpts.reshape(B, 3, -1), pose, scale, canonical_pose, tri_plane.to(dt), weights,
-                            use_grid_sample, **qkw)
+    cden, _, cvalid, ctaps = query(cpts.reshape(B, 3, -1), pose, scale, canonical_pose, tri_plane.to(dt), weights,
+                                   use_grid_sample, return_taps=True, **qkw)
     cden = cden.reshape(B, n, Nc)
     _, cw = ray_weights(cden, cdepth, render_scale)
     cws = smooth_weights(cw)
     if bins is None:
         bins = draw_bins(cws, Nf, Nc, generator)
     fdepth, fpts = fine_points(bins.to(dt), dmin, dmax, start, end)
-    fden, fcol, fvalid = query(fpts.reshape(B, 3, -1), pose, scale, canonical_pose, tri_plane.to(dt), weights,
-                               use_grid_sample, **qkw)
+    fden, fcol, fvalid, ftaps = query(fpts.reshape(B, 3, -1), pose, scale, canonical_pose, tri_plane.to(dt), weights,
+                                      use_grid_sample, return_taps=True, **qkw)
     fden = fden.reshape(B, n, Nf)
     fcol = fcol.reshape(B, 3, n, Nf)
     rc, rm, rdisp, fw = composite(fden, fcol, fdepth, render_scale)
@@ -493,7 +497,9 @@ def render(image_coord: torch.Tensor, pose_parts: torch.Tensor, bone_length_part
                 "ray_validity": rvalid, "coarse_depth": cdepth, "coarse_density": cden,
                 "coarse_weights_smooth": cws, "coarse_valid": cvalid.reshape(B, -1, n, Nc),
                 "bins": bins, "fine_depth": fdepth, "fine_density": fden, "fine_color": fcol,
-                "fine_valid": fvalid.reshape(B, -1, n, Nf), "fine_weights": fw}
+                "fine_valid": fvalid.reshape(B, -1, n, Nf), "fine_weights": fw,
+                "coarse_signed_density": ctaps["signed_density"].reshape(B, n, Nc),
+                "fine_signed_density": ftaps["signed_density"].reshape(B, n, Nf)}
         return rc, rm, rdisp, taps
     return rc, rm, rdisp
 

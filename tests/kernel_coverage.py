@@ -151,11 +151,15 @@ KERNEL_TESTS = {
     f"void enarf::render_kernel<0, 2>({_RA})": [
         "test_gpu_parity::test_render_vs_oracle_and_golden", "test_gpu_parity::test_both_march_kernels_give_the_same_bits",
         "test_gpu_forward_f64::test_forward_march_vs_float64"],
-    f"void enarf::render_kernel<1, 1>({_RA})": ["test_gpu_parity::test_bf16_modes_both_march_kernels_vs_oracle"],
-    f"void enarf::render_kernel<1, 2>({_RA})": ["test_gpu_parity::test_bf16_modes_both_march_kernels_vs_oracle"],
-    f"void enarf::render_kernel<2, 1>({_RA})": ["test_gpu_parity::test_bf16_modes_both_march_kernels_vs_oracle"],
+    f"void enarf::render_kernel<1, 1>({_RA})": ["test_gpu_parity::test_bf16_modes_both_march_kernels_vs_oracle",
+        "test_gpu_forward_f64::test_forward_march_vs_float64"],
+    f"void enarf::render_kernel<1, 2>({_RA})": ["test_gpu_parity::test_bf16_modes_both_march_kernels_vs_oracle",
+        "test_gpu_forward_f64::test_forward_march_vs_float64"],
+    f"void enarf::render_kernel<2, 1>({_RA})": ["test_gpu_parity::test_bf16_modes_both_march_kernels_vs_oracle",
+        "test_gpu_forward_f64::test_forward_march_vs_float64"],
     f"void enarf::render_kernel<2, 2>({_RA})": [
-        "test_gpu_parity::test_bf16_modes_both_march_kernels_vs_oracle", "test_gpu_configs::test_c4_256_nc72_nf96_bf16_early_termination"],
+        "test_gpu_parity::test_bf16_modes_both_march_kernels_vs_oracle", "test_gpu_configs::test_c4_256_nc72_nf96_bf16_early_termination",
+        "test_gpu_forward_f64::test_forward_march_vs_float64"],
     f"void enarf::render_kernel<3, 1>({_RA})": [
         "test_gpu_parity::test_render_vs_oracle_and_golden", "test_gpu_parity::test_both_march_kernels_give_the_same_bits",
         "test_gpu_forward_f64::test_forward_march_vs_float64"],
@@ -167,10 +171,14 @@ KERNEL_TESTS = {
     f"void enarf::march_kernel<0, 2, 12>({_RA}, int, unsigned int*)": [
         "test_gpu_parity::test_both_march_kernels_give_the_same_bits", "test_gpu_parity::test_render_sample_count_variants_vs_oracle",
         "test_gpu_forward_f64::test_forward_march_vs_float64"],
-    f"void enarf::march_kernel<1, 1, 12>({_RA}, int, unsigned int*)": ["test_gpu_parity::test_bf16_modes_both_march_kernels_vs_oracle"],
-    f"void enarf::march_kernel<1, 2, 12>({_RA}, int, unsigned int*)": ["test_gpu_parity::test_bf16_modes_both_march_kernels_vs_oracle"],
-    f"void enarf::march_kernel<2, 1, 12>({_RA}, int, unsigned int*)": ["test_gpu_parity::test_bf16_modes_both_march_kernels_vs_oracle"],
-    f"void enarf::march_kernel<2, 2, 12>({_RA}, int, unsigned int*)": ["test_gpu_parity::test_bf16_modes_both_march_kernels_vs_oracle"],
+    f"void enarf::march_kernel<1, 1, 12>({_RA}, int, unsigned int*)": ["test_gpu_parity::test_bf16_modes_both_march_kernels_vs_oracle",
+        "test_gpu_forward_f64::test_forward_march_vs_float64"],
+    f"void enarf::march_kernel<1, 2, 12>({_RA}, int, unsigned int*)": ["test_gpu_parity::test_bf16_modes_both_march_kernels_vs_oracle",
+        "test_gpu_forward_f64::test_forward_march_vs_float64"],
+    f"void enarf::march_kernel<2, 1, 12>({_RA}, int, unsigned int*)": ["test_gpu_parity::test_bf16_modes_both_march_kernels_vs_oracle",
+        "test_gpu_forward_f64::test_forward_march_vs_float64"],
+    f"void enarf::march_kernel<2, 2, 12>({_RA}, int, unsigned int*)": ["test_gpu_parity::test_bf16_modes_both_march_kernels_vs_oracle",
+        "test_gpu_forward_f64::test_forward_march_vs_float64"],
     f"void enarf::march_kernel<3, 1, 12>({_RA}, int, unsigned int*)": ["test_gpu_parity::test_both_march_kernels_give_the_same_bits",
         "test_gpu_forward_f64::test_forward_march_vs_float64"],
     f"void enarf::march_kernel<3, 2, 12>({_RA}, int, unsigned int*)": ["test_gpu_parity::test_both_march_kernels_give_the_same_bits",
@@ -182,10 +190,12 @@ KERNEL_TESTS = {
         "test_gpu_forward_f64::test_query_fwd_placed_points_vs_float64"],
     f"void enarf::query_kernel<1, false>({_QA})": ["test_gpu_parity::test_query_debug_and_production_kernels_in_bf16_modes"],
     f"void enarf::query_kernel<1, true>({_QA})": [
-        "test_gpu_parity::test_query_vs_oracle_and_golden", "test_gpu_parity::test_query_debug_and_production_kernels_in_bf16_modes"],
+        "test_gpu_parity::test_query_vs_oracle_and_golden", "test_gpu_parity::test_query_debug_and_production_kernels_in_bf16_modes",
+        "test_gpu_forward_f64::test_query_fwd_placed_points_vs_float64"],
     f"void enarf::query_kernel<2, false>({_QA})": [
         "test_gpu_parity::test_query_bf16_mode_is_close", "test_gpu_parity::test_query_debug_and_production_kernels_in_bf16_modes"],
-    f"void enarf::query_kernel<2, true>({_QA})": ["test_gpu_parity::test_query_debug_and_production_kernels_in_bf16_modes"],
+    f"void enarf::query_kernel<2, true>({_QA})": ["test_gpu_parity::test_query_debug_and_production_kernels_in_bf16_modes",
+        "test_gpu_forward_f64::test_query_fwd_placed_points_vs_float64"],
     f"void enarf::query_kernel<3, false>({_QA})": [
         "test_gpu_api::test_gan_generator_forward_matches_oracle", "test_gpu_api::test_model_query_entry_point_matches_reference_golden"],
     f"void enarf::query_kernel<3, true>({_QA})": [

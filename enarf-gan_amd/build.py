@@ -42,6 +42,7 @@ SIDE_LIBRARIES = {
     "geom": (["enarf_geom.hip"], "enarf_geom.h"),          # depth, point and normal maps of a march, running depth error
     "pgrad": (["enarf_pgrad.hip"], "enarf_pgrad.h"),       # the query's gradient for the sample points and the part frames
     "scene": (["enarf_scene.hip"], "enarf_scene.h"),       # several avatars marched on the same rays, composed into one image
+    "sgrad": (["enarf_sgrad.hip"], "enarf_sgrad.h"),       # the scene composite's gradient for the avatars' densities and colours
     "skin": (["enarf_skin.hip"], "enarf_skin.h"),          # skin weights of mesh vertices, linear-blend posing of the mesh
 }
 ALL_LIBRARIES = {**LIBRARIES, **SIDE_LIBRARIES}

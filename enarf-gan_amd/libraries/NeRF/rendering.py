@@ -263,6 +263,27 @@ def composite_fine(density: torch.Tensor, color: torch.Tensor, depth: torch.Tens
     return (w[:, None] * color[..., :-1]).sum(dim=-1), w.sum(dim=-1), (w * 1 / depth[..., :-1]).sum(dim=-1), w
 
 
+def _fixed_samples(model, image_coord, inv_intrinsics, parts, tri, feat_cl, pack, Nc, Nf, render_scale, bins, seed):
+    """The sample positions a posable render holds fixed, from one march with its taps (call under no_grad): image_coord
+    (B, 1, 3, n) or (B, 3, n), inv_intrinsics (3, 3) or (B, 3, 3) -> (the march's taps, fine_points (B, 3, n Nf) formed from
+    bins, depth_min and depth_max as return_intermediate forms them, fine_depth (B, n, Nf))."""
+    B, n = image_coord.shape[0], image_coord.shape[-1]
+    out = ops.render_fwd(image_coord, inv_intrinsics, parts, model.canonical_pose, tri, feat_cl, pack, Nc, Nf,
+                         render_scale=render_scale, bins=bins, seed=seed, mlp_mode=model.mlp_mode, debug=True,
+                         **model.kernel_flags())
+    t = out.taps
+    coord = image_coord.reshape(B, 3, n).to(torch.float32)
+    Ki = inv_intrinsics.to(torch.float32)
+    if Ki.dim() == 2:
+        Ki = Ki[None].expand(B, -1, -1)
+    ray = torch.einsum("bij,bjn->bin", Ki, coord)
+    b_ = t["bins"][:, None]                                                # (B, 1, n, Nf)
+    start, end = (t["depth_min"][:, None] * ray)[..., None], (t["depth_max"][:, None] * ray)[..., None]
+    fine_points = (start * (1 - b_) + end * b_).reshape(B, 3, n * Nf)
+    fine_depth = t["depth_min"][..., None] * (1 - t["bins"]) + t["depth_max"][..., None] * t["bins"]
+    return t, fine_points, fine_depth
+
+
 def render_posable(model, image_coord: torch.Tensor, pose_to_camera: torch.Tensor, inv_intrinsics: torch.Tensor,
                    render_scale: float = 1, Nc: int = 64, Nf: int = 128, model_input: Dict = {},
                    bins: Optional[torch.Tensor] = None, seed: Optional[int] = None):
@@ -288,19 +309,8 @@ def render_posable(model, image_coord: torch.Tensor, pose_to_camera: torch.Tenso
         parts = _parts_from_part_poses(model, pose_to_camera.detach(), model_input["bone_length"].detach())
         mi = dict(model_input)
         tri, feat_cl = model._tri_plane_pair(mi)
-        out = ops.render_fwd(image_coord, inv_intrinsics, parts, model.canonical_pose, tri, feat_cl,
-                             model._mlp_pack(z_rend.detach()), Nc, Nf, render_scale=render_scale, bins=bins, seed=seed,
-                             mlp_mode=model.mlp_mode, debug=True, **model.kernel_flags())
-        t = out.taps
-        coord = image_coord.reshape(B, 3, n).to(torch.float32)
-        Ki = inv_intrinsics.to(torch.float32)
-        if Ki.dim() == 2:
-            Ki = Ki[None].expand(B, -1, -1)
-        ray = torch.einsum("bij,bjn->bin", Ki, coord)
-        b_ = t["bins"][:, None]                                                # (B, 1, n, Nf)
-        start, end = (t["depth_min"][:, None] * ray)[..., None], (t["depth_max"][:, None] * ray)[..., None]
-        fine_points = (start * (1 - b_) + end * b_).reshape(B, 3, n * Nf)
-        fine_depth = t["depth_min"][..., None] * (1 - t["bins"]) + t["depth_max"][..., None] * t["bins"]
+        t, fine_points, fine_depth = _fixed_samples(model, image_coord, inv_intrinsics, parts, tri, feat_cl,
+                                                    model._mlp_pack(z_rend.detach()), Nc, Nf, render_scale, bins, seed)
         live = t["ray_validity"].to(torch.float32) if B == 1 else None         # rendering.py:107-110
     frames = torch.cat([pose_to_camera[:, :, :3, :3], pose_to_camera[:, :, :3, 3:] * cs], dim=-1)
     density, color = model.query_posable(fine_points, frames, model_input)
@@ -384,3 +394,59 @@ def render_scene(model, image_coord: torch.Tensor, pose_to_camera: torch.Tensor,
             marches.append(_march_taps(model, image_coord, inv_intrinsics, parts[a:b], tri, feat_cl, pack, Nc, Nf,
                                        render_scale, seed, flags))
         return composite_marches(model, marches, 0, render_scale, threshold)
+
+
+def render_scene_posable(model, image_coord: torch.Tensor, pose_to_camera: torch.Tensor, inv_intrinsics: torch.Tensor,
+                         render_scale: float = 1, Nc: int = 64, Nf: int = 128, model_input: Dict = {},
+                         avatars_per_batch: Optional[int] = None, seed: Optional[int] = None,
+                         bins: Optional[torch.Tensor] = None):
+    """render_scene for poses that require gradients: the arguments of render_scene, with pose_to_camera (K, P, 4, 4) part
+    frames and model_input["bone_length"] that may require gradients; `bins` (K, n, Nf) gives the importance samples
+    -> colour (1, 3, n), mask (1, n), disparity (1, n) of the scene, differentiable with respect to pose_to_camera and
+    bone_length, and to the tri-planes, z_rend and the StyledMLP where they require gradients.
+
+    Contract: render_posable's, the gradient of the image AT FIXED SAMPLE POSITIONS. The K avatars are marched on the same
+    rays under no_grad (avatars_per_batch at a time, as render_scene marches them), which fixes every ray's depth
+    range, its validity and its importance samples; every avatar's fine points and fine depths are formed from them as
+    render_posable forms them and are constants. One model.query_posable call on the K avatars as a batch carries the
+    gradient to the articulation, and ops.scene_composite_posable (the forward of render_scene's composite, its
+    backward one launch of libenarf_sgrad.so) composes the K sample lists: where bodies interleave in depth, each
+    avatar's gradient sees the other's occlusion. The forward values are render_scene's on the same seed up to the
+    difference between the march's own taps and query_posable's outputs (fp32 rounding). model.buffers_tensors gets
+    instance_mass (1, K, n), which carries the gradient as well, instance (1, n) int32 and skipped (1, n) int32 at a
+    threshold of 0.5, fine_points (K, 3, n Nf), fine_depth (K, 1, n, Nf) and bins."""
+    assert pose_to_camera.shape[1] == model.num_bone
+    K, n = pose_to_camera.shape[0], image_coord.shape[-1]
+    per = K if avatars_per_batch is None else int(avatars_per_batch)
+    if per < 1:
+        raise ValueError(f"render_scene_posable: avatars_per_batch {avatars_per_batch} < 1")
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    cs = model.coordinate_scale
+    coord = image_coord.reshape(1, 3, n)
+    Ki = inv_intrinsics.reshape(-1, 3, 3)[:1]
+    with torch.no_grad():
+        parts = _parts_from_part_poses(model, pose_to_camera.detach(), model_input["bone_length"].detach())
+        taps = []
+        for a in range(0, K, per):
+            b = min(a + per, K)
+            mi = {k: (v.detach()[a:b] if isinstance(v, torch.Tensor) and v.dim() > 0 and v.shape[0] == K else v)
+                  for k, v in model_input.items()}
+            tri, feat_cl = model._tri_plane_pair(mi)
+            t, points, depth = _fixed_samples(model, coord.expand(b - a, -1, -1), Ki.expand(b - a, -1, -1), parts[a:b], tri,
+                                              feat_cl, model._mlp_pack(mi["z_rend"]), Nc, Nf, render_scale,
+                                              None if bins is None else bins[a:b], seed)
+            taps.append((points, depth, t["ray_validity"], t["bins"]))
+        fine_points, fine_depth, valid, bins_used = (torch.cat([t[i] for t in taps], dim=0) for i in range(4))
+    frames = torch.cat([pose_to_camera[:, :, :3, :3], pose_to_camera[:, :, :3, 3:] * cs], dim=-1)
+    density, color = model.query_posable(fine_points, frames, model_input)
+    density, color = density.reshape(1, K, n, Nf), color.reshape(1, K, 3, n, Nf)
+    rc, rm, rd, mass = ops.scene_composite_posable(fine_depth[None], density, color, valid[None], render_scale)
+    with torch.no_grad():
+        owner = ops.scene_composite(fine_depth[None], density.detach(), color.detach(), valid[None],
+                                    render_scale=render_scale, want=("instance", "skipped"))
+    if not hasattr(model, "buffers_tensors"):
+        model.buffers_tensors = {}
+    model.buffers_tensors.update(instance_mass=mass, instance=owner.instance, skipped=owner.skipped, bins=bins_used,
+                                 fine_depth=fine_depth[:, None], fine_points=fine_points)
+    return rc, rm, rd

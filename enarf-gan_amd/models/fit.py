@@ -1,7 +1,9 @@
 """Fitting the pose of a posable field to a picture: `PoseCorrection`, per-frame residuals on the 24 joints' local rotations
 and the root's translation, and `fit_pose`, Adam on one through `render_posable` and the photometric loss. The gradient
 reaches the residuals through torch's own graph from the (B, P, 16) part records, whose gradient is the HIP kernel's
-(ops.query_pose_bwd); nothing in the loop reads a value back from the device."""
+(ops.query_pose_bwd); nothing in the loop reads a value back from the device. `fit_scene` is the same loop for one picture
+with K people in it, through `render_scene_posable`: the avatars are composed depth-correctly and the composite's own
+gradient is a HIP kernel as well (ops.scene_composite_bwd)."""
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -122,6 +124,74 @@ def fit_pose(gen, target_img: torch.Tensor, target_mask: torch.Tensor, pose_to_c
             color = color + background * (1 - mask[:, None])
             loss_color, loss_mask = ops.photometric_loss(ray_idx, color, mask, target_img, target_mask, loss_type)
             loss = loss_color + loss_mask
+            history[i] = loss.detach()
+            loss.backward()
+            optimizer.step()
+    finally:
+        for p in frozen:
+            p.requires_grad_(True)
+    with torch.no_grad():
+        return correction(pose_to_camera).detach(), history
+
+
+def fit_scene(gen, target_img: torch.Tensor, target_mask: torch.Tensor, pose_to_camera: torch.Tensor,
+              bone_length: torch.Tensor, z, inv_intrinsics: torch.Tensor, steps: int = 100, lr: float = 1e-2,
+              n_rays: int = 1024, Nc: Optional[int] = None, Nf: Optional[int] = None, background: float = -1.0,
+              loss_type: str = "mse", seed: int = 0, correction: Optional[PoseCorrection] = None,
+              target_instance: Optional[torch.Tensor] = None, instance_weight: float = 1.0,
+              truncation_psi: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fit_pose for one picture with K people in it: the 24-joint poses pose_to_camera (K, 24, 4, 4) of K avatars of a
+    trained field (bone_length and z of batch K, z as fit_pose takes it) are fitted to target_img (1, 3, S, S) and
+    target_mask (1, S, S), the mask of the whole scene. Adam on one PoseCorrection(K, ...) (one frame an avatar), `steps`
+    steps of: n_rays rays by mask_based_sampler on target_mask, render_scene_posable over `background` (the K avatars
+    composed depth-correctly, each one's gradient through the HIP backward of the composite), ops.photometric_loss.
+    Where target_instance (1, S, S) is given (the avatar that owns each pixel, -1 for none), instance_weight times the
+    mean squared difference between instance_mass[k] and (target_instance == k) on the sampled rays is added, in torch.
+    The field is held fixed and its tri-planes are produced once per avatar. The importance samples of step i are drawn
+    with seed + i. No host synchronisation inside the loop. Returns (the fitted poses (K, 24, 4, 4), detached, and the
+    loss of every step (steps,) as a device tensor)."""
+    from ..libraries.NeRF.rendering import render_scene_posable
+    nerf = getattr(gen, "nerf", gen)
+    samples = getattr(gen, "_samples", {}) if nerf is not gen else {}
+    Nc = int(Nc if Nc is not None else samples.get("Nc", nerf.config.Nc))
+    Nf = int(Nf if Nf is not None else samples.get("Nf", nerf.config.Nf))
+    z_tri, z_rend = z if isinstance(z, (tuple, list)) else (z, z)
+    K = pose_to_camera.shape[0]
+    dev = pose_to_camera.device
+    if target_img.shape[0] != 1 or target_mask.shape[0] != 1:
+        raise ValueError(f"fit_scene takes one picture: target_img (1, 3, S, S) and target_mask (1, S, S), got "
+                         f"{tuple(target_img.shape)} and {tuple(target_mask.shape)}")
+    if correction is None:
+        correction = PoseCorrection(K, nerf.parent_id, pose_to_camera.shape[1]).to(dev)
+    owner = None
+    if target_instance is not None:
+        owner = target_instance.reshape(1, -1).to(dev)
+        ids = torch.arange(K, device=dev)[None, :, None]
+    optimizer = torch.optim.Adam(correction.parameters(), lr=lr)
+    history = torch.zeros(steps, dtype=torch.float32, device=dev)
+    frozen = [p for p in nerf.parameters() if p.requires_grad]
+    for p in frozen:
+        p.requires_grad_(False)
+    try:
+        tri = None
+        if not (nerf.uses_warp or nerf.constant_trimask):          # those producers emit their planes inside the render
+            with torch.no_grad():
+                tri = nerf.compute_tri_plane_feature(z_tri, nerf.transform_pose(pose_to_camera, bone_length)[1], truncation_psi)
+        for i in range(steps):
+            optimizer.zero_grad()
+            ray_idx, pixels = mask_based_sampler(target_mask, n_rays)
+            pose_parts, bl_parts = nerf.transform_pose(correction(pose_to_camera), bone_length)
+            mi = {"z": z_tri, "z_rend": z_rend, "bone_length": bl_parts, "truncation_psi": truncation_psi}
+            if tri is not None:
+                mi["tri_plane_feature"] = tri
+            color, mask, _ = render_scene_posable(nerf, pixels, pose_parts, inv_intrinsics, Nc=Nc, Nf=Nf, model_input=mi,
+                                                  seed=seed + i)
+            color = color + background * (1 - mask[:, None])
+            loss_color, loss_mask = ops.photometric_loss(ray_idx, color, mask, target_img, target_mask, loss_type)
+            loss = loss_color + loss_mask
+            if owner is not None:
+                wanted = (torch.gather(owner, 1, ray_idx)[:, None] == ids).to(torch.float32)           # (1, K, n)
+                loss = loss + instance_weight * ((nerf.buffers_tensors["instance_mass"] - wanted) ** 2).mean()
             history[i] = loss.detach()
             loss.backward()
             optimizer.step()

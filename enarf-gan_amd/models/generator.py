@@ -453,6 +453,44 @@ class TriNARFGenerator(_RendererShell):
         instance = nerf.buffers_tensors["instance"].reshape(1, S, S)
         return image, alpha, instance, self._instance_image(instance, K)
 
+    def render_scene_posable(self, pose_to_camera, bone_length, z, inv_intrinsics, truncation_psi=1, background="first",
+                             pixels=None, avatars_per_batch=None, seed=None):
+        """render_scene for poses that require gradients: pose_to_camera (K, J, 4, 4) and bone_length may require them and
+        receive the gradient of the image at fixed sample positions (rendering.render_scene_posable: the HIP pose
+        gradient of every avatar's query, the HIP backward of the composite). `pixels` (1, 1, 3, n) names the rays
+        (default: the whole S x S frame, n = S S) -> (image (1, 3, n), mask (1, n)), image = colour + (1 - mask)
+        background. On the whole frame the background is _scene_backdrop's; on given pixels it is a number or a
+        (1, 3, n) tensor, one colour a ray. instance_mass (differentiable), instance and skipped are left in
+        self.nerf.buffers_tensors. The tri-planes are produced once, for the march and the query alike."""
+        from ..libraries.NeRF.rendering import render_scene_posable
+        nerf, S, K = self.nerf, self.size, pose_to_camera.shape[0]
+        if not (z.shape[0] == K and bone_length.shape[0] == K):
+            raise AssertionError(f"render_scene_posable takes z and bone_length of batch K = {K}, one entry an avatar")
+        dev = pose_to_camera.device
+        whole = pixels is None
+        if whole:
+            _, pixels = self.ray_sampler(S, S, 1, device=dev)
+        z_nerf, z_render, z_bg = self._latent_parts(z)
+        K_inv = torch.as_tensor(inv_intrinsics).float().to(dev)
+        pose_parts, bl_parts = nerf.transform_pose(pose_to_camera, bone_length)
+        model_input = {"z": z_nerf, "z_rend": z_render, "bone_length": bl_parts, "truncation_psi": truncation_psi}
+        if not (nerf.uses_warp or nerf.constant_trimask):
+            model_input["tri_plane_feature"] = nerf.compute_tri_plane_feature(z_nerf, bl_parts, truncation_psi)
+        color, mask, _ = render_scene_posable(nerf, pixels, pose_parts, K_inv, model_input=model_input,
+                                              avatars_per_batch=avatars_per_batch, seed=seed, **self._samples)
+        if isinstance(background, torch.Tensor) and not whole:
+            if tuple(background.shape) != tuple(color.shape):
+                raise ValueError(f"render_scene_posable: a background on given pixels is {tuple(color.shape)}, got "
+                                 f"{tuple(background.shape)}")
+            backdrop = background.to(device=dev, dtype=torch.float32)
+        elif isinstance(background, str) and not whole:
+            raise ValueError("render_scene_posable: background 'first' needs the whole frame; pass a number or a (1, 3, n) tensor")
+        else:
+            backdrop = self._scene_backdrop(background, z_bg, z_render, dev)
+            if isinstance(backdrop, torch.Tensor):
+                backdrop = backdrop.reshape(1, 3, S * S)
+        return color + (1 - mask[:, None]) * backdrop, mask
+
     def render_scene_animation(self, key_poses, bone_length, intrinsics, z, num=100, loop=True, orbit=None, truncation_psi=0.4,
                                frames_per_batch=8, background="first", threshold=0.5):
         """K identities in motion in front of one camera, on the device from end to end: (frames (num, S, S, 3) uint8,

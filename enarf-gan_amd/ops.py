@@ -1040,3 +1040,38 @@ def scene_composite(depth: torch.Tensor, density: torch.Tensor, color: torch.Ten
     it does not take."""
     from . import _scene_lib
     return _scene_lib.scene_composite(depth, density, color, valid, render_scale, threshold, want, out)
+
+
+# ------------------------------------------------------------------------------------------------- differentiable scenes
+from ._sgrad_lib import SceneGradients  # noqa: E402,F401  (scene_composite_bwd's result)
+
+
+def scene_composite_bwd(depth: torch.Tensor, density: torch.Tensor, color: torch.Tensor, valid: Optional[torch.Tensor] = None,
+                        render_scale=1.0, g_color: Optional[torch.Tensor] = None, g_mask: Optional[torch.Tensor] = None,
+                        g_disparity: Optional[torch.Tensor] = None, g_instance_mass: Optional[torch.Tensor] = None,
+                        want=("density", "color"), out=None):
+    """Backward of scene_composite with respect to the avatars' densities and colours, in one launch of libenarf_sgrad.so:
+    the namedtuple SceneGradients (density (F, K, n, Nf), color (F, K, 3, n, Nf) fp32); a field not named in `want` is None
+    and is not written. depth, density, color, valid and render_scale as scene_composite takes them (without the frame
+    axis (K, n, Nf) is one frame and the outputs lose it too); the upstream gradients g_color (F, 3, n), g_mask and
+    g_disparity (F, n), g_instance_mass (F, K, n) fp32, each of which may be None (zeros), at least one given. The
+    gradient is that of g_color . colour + g_mask mask + g_disparity disparity + sum_k g_instance_mass[k]
+    instance_mass[k] at fixed depths (include/enarf_sgrad.h has the formulas); at a density of exactly 0 it is the
+    derivative from inside s >= 0. Every entry is written: an avatar's last sample, an avatar that takes no part on a ray
+    and a ray nobody takes part on get exact zeros. `out` maps names of `want` to contiguous tensors to write into.
+    Computed in fp64 from the fp32 inputs without atomics, bit-identical from run to run, nothing synchronises, F n = 0
+    launches nothing. NotImplementedError for K outside [1, 8], Nf outside [2, 128] and K Nf > 512; ValueError for
+    shapes or dtypes it does not take, an empty `want` and a call without any upstream gradient."""
+    from . import _sgrad_lib
+    return _sgrad_lib.scene_composite_bwd(depth, density, color, valid, render_scale, g_color, g_mask, g_disparity,
+                                          g_instance_mass, want, out)
+
+
+def scene_composite_posable(depth: torch.Tensor, density: torch.Tensor, color: torch.Tensor,
+                            valid: Optional[torch.Tensor] = None, render_scale=1.0):
+    """scene_composite for densities and colours that require gradients: (color (F, 3, n), mask (F, n), disparity (F, n),
+    instance_mass (F, K, n)) through a torch.autograd.Function whose forward is scene_composite on the detached inputs,
+    bit for bit, and whose backward is scene_composite_bwd. The depths are constants: a depth that requires a gradient
+    raises NotImplementedError. scene_composite itself keeps refusing inputs that require gradients."""
+    from . import _sgrad_lib
+    return _sgrad_lib.scene_composite_posable(depth, density, color, valid, render_scale)

@@ -11,7 +11,9 @@ is generated inside `enarf_query_fwd` (lattice mode, density only, one launch; o
 image of the mesh in those colours or in the colours of its part labels (rasterize_mesh, then the deferred shading of
 libenarf_paint.so); `export_obj` and `export_ply` carry the colours and labels out. `extract_rigged_mesh` binds such a mesh
 to the model's parts (a `RiggedMesh`: extract_mesh plus one skin-weight launch of libenarf_skin.so), `skin_mesh` poses it by
-linear-blend skinning without a new extraction, and `export_glb` writes it as a skinned binary glTF.
+linear-blend skinning without a new extraction, and `export_glb` writes it as a skinned binary glTF. `bake_texture` gives a
+mesh a texture atlas of the field's colour (a `TextureAtlas`: libenarf_bake.so for the texel points and the texture, the
+query kernel for the colours), `paint_textured_mesh` draws the mesh with it, and `export_glb` embeds it and animation clips.
 """
 from __future__ import annotations
 
@@ -165,12 +167,91 @@ def extract_mesh(model, pose_to_camera: torch.Tensor, center: torch.Tensor, voxe
 
 
 @dataclasses.dataclass
+class TextureAtlas:
+    """The texture of a mesh in the per-triangle atlas of include/enarf_bake.h: texture (A, A, 4) uint8 RGBA (alpha 255 on
+    the texels a triangle owns, 0 elsewhere), optionally texture_f32 (A, A, 3) fp32, the same colours before they were
+    quantised, num_triangles T, size A and cell c (ops.bake_layout(T, A).cell). The UVs are not stored: atlas_uv(T, A)."""
+    texture: torch.Tensor
+    texture_f32: Optional[torch.Tensor]
+    num_triangles: int
+    size: int
+    cell: int
+
+
+def atlas_uv(T: int, size: int):
+    """(T, 3, 2) fp32 numpy: the UV of every triangle corner in [0, 1], u to the right and v down from the top row (glTF's
+    convention), computed on the host from the layout alone"""
+    import numpy as np
+    from ..._bake_lib import atlas_corners
+    return (atlas_corners(T, size) / float(int(size))).astype(np.float32)
+
+
+@torch.no_grad()
+def bake_texture(model, pose_to_camera, vertices: torch.Tensor, triangles: torch.Tensor, model_input: Dict = {},
+                 size: int = 1024, color: str = "field", palette=None, color_fn=None, want_float: bool = False,
+                 band_rows: Optional[int] = None) -> TextureAtlas:
+    """The texture atlas of a mesh: ops.bake_points gives the surface point of every texel, band of rows by band (at most
+    2^22 texels a band by default, so the peak memory is bounded at 8192^2), the colour there comes from
+      color="field"  one ops.query_fwd launch a band with the scaling and flags of vertex_colors (a band the layout leaves
+                     without an owned texel - the margin, cells past the last triangle - is skipped);
+      color="parts"  one ops.part_labels launch a band, drawn in `palette` ((semantic_palette + 1) / 2 by default);
+      color_fn       a function points (M, 3) -> colours (M, 3) fp32 in [0, 1], instead of the model (which may be None),
+    and ops.bake_resolve writes the band's rows of the texture. vertices (V, 3) fp32 in camera space and triangles (T, 3)
+    int64 on the device, pose_to_camera (1, P, 4, 4) part frames with UNSCALED translation, as for vertex_colors."""
+    if color_fn is None and color not in ("field", "parts"):
+        raise ValueError(f"color is 'field' (the radiance field's colour) or 'parts' (the part labels), got {color!r}")
+    T, A = triangles.shape[0], int(size)
+    lay = ops.bake_layout(T, A)
+    dev = vertices.device
+    texture = torch.empty(A, A, 4, dtype=torch.uint8, device=dev)
+    texture_f32 = torch.empty(A, A, 3, dtype=torch.float32, device=dev) if want_float else None
+    per = max(1, min(A, (1 << 22) // A)) if band_rows is None else max(1, int(band_rows))
+    if color_fn is None:
+        from ..NeRF.rendering import _parts_from_part_poses, semantic_palette
+        cs = model.coordinate_scale
+        flags = model.kernel_flags()
+        parts = _parts_from_part_poses(model, pose_to_camera, model_input["bone_length"])
+        if color == "field":
+            tri, feat_cl = model._tri_plane_pair(model_input)
+            pack = model._mlp_pack(model_input["z_rend"])
+        else:
+            tri = _mask_tri_plane(model, model_input)
+            if palette is None:
+                palette = (semantic_palette(model.num_bone, dev) + 1) / 2
+    for a in range(0, A, per):
+        b = min(a + per, A)
+        out = (texture[a:b], None if texture_f32 is None else texture_f32[a:b])
+        if color_fn is None and color == "field" and (a >= lay.cells_per_row * lay.cell
+                                                      or 2 * (a // lay.cell) * lay.cells_per_row >= T):
+            texture[a:b] = 0                     # rows of the margin or of cells past the last triangle: what resolve gives
+            if texture_f32 is not None:
+                texture_f32[a:b] = 0
+            continue
+        baked = ops.bake_points(vertices, triangles, A, rows=(a, b))
+        if color_fn is not None:
+            rgb = color_fn(baked.points.t()).to(torch.float32).t().contiguous()
+            ops.bake_resolve(baked.texel_face, color=rgb, unit=True, out=out)
+        elif color == "parts":
+            points = (baked.points * cs if cs != 1 else baked.points)[None]
+            labels = ops.part_labels(points, parts, model.canonical_pose, tri, clamp_mask=flags["clamp_mask"],
+                                     uniform_part_weight=flags["uniform_part_weight"])[0]
+            ops.bake_resolve(baked.texel_face, labels=labels.reshape(-1), palette=palette.float(), out=out)
+        else:
+            points = (baked.points * cs if cs != 1 else baked.points)[None]
+            _, rgb = ops.query_fwd(points, parts, model.canonical_pose, tri, feat_cl, pack, mlp_mode=model.mlp_mode,
+                                   need_color=True, **flags)
+            ops.bake_resolve(baked.texel_face, color=rgb[0], out=out)
+    return TextureAtlas(texture, texture_f32, T, A, lay.cell)
+
+
+@dataclasses.dataclass
 class RiggedMesh:
     """A mesh bound to the parts of the model it was extracted from: vertices (V, 3) fp32 in camera units in the rest
     pose, triangles (T, 3) int64, joints (V, K) int32 (-1: unused slot) and weights (V, K) fp32 by descending weight,
     kept_mass (V,) fp32 (the share of the part-probability mass the K kept parts carry; 0: no part contains the vertex, it
     follows the nearest), rest_pose (1, P, 4, 4) the rest part frames with UNSCALED translation, rest_bone_length
-    (1, P, 1), and optionally colors (V, 3) fp32 in [0, 1] and labels (V,) int32."""
+    (1, P, 1), and optionally colors (V, 3) fp32 in [0, 1], labels (V,) int32 and texture, the TextureAtlas of the mesh
+    baked in the rest pose."""
     vertices: torch.Tensor
     triangles: torch.Tensor
     joints: torch.Tensor
@@ -180,6 +261,7 @@ class RiggedMesh:
     rest_bone_length: torch.Tensor
     colors: Optional[torch.Tensor] = None
     labels: Optional[torch.Tensor] = None
+    texture: Optional[TextureAtlas] = None
 
 
 def _mask_tri_plane(model, model_input: Dict) -> torch.Tensor:
@@ -196,11 +278,13 @@ def _mask_tri_plane(model, model_input: Dict) -> torch.Tensor:
 @torch.no_grad()
 def extract_rigged_mesh(model, pose_to_camera: torch.Tensor, center: torch.Tensor, voxel_size: float = 0.003,
                         mesh_th: float = 15, model_input: Dict = {}, max_influences: int = 4, return_colors: bool = False,
-                        return_part_labels: bool = False) -> RiggedMesh:
+                        return_part_labels: bool = False, texture_size: Optional[int] = None,
+                        texture_color: str = "field") -> RiggedMesh:
     """extract_mesh in the pose pose_to_camera (1, P, 4, 4) - the rest pose of the rig - plus one ops.skin_weights launch
     over the vertex array: every vertex bound to the max_influences (4 or 8) parts of the largest part probability among
     the parts whose cube contains it. `return_colors` and `return_part_labels` fill the record's colors and labels as
-    extract_mesh returns them. The mesh is posed by skin_mesh and written out by export_glb."""
+    extract_mesh returns them; `texture_size` fills its texture: bake_texture of the mesh in this pose, in `texture_color`
+    ("field" or "parts"). The mesh is posed by skin_mesh and written out by export_glb."""
     from ..NeRF.rendering import _parts_from_part_poses
     got = extract_mesh(model, pose_to_camera, center, voxel_size, mesh_th, model_input, return_part_labels, return_colors)
     vertices, triangles, extra = got[0], got[1], list(got[2:])
@@ -213,8 +297,11 @@ def extract_rigged_mesh(model, pose_to_camera: torch.Tensor, center: torch.Tenso
                                              max_influences=max_influences, clamp_mask=flags["clamp_mask"],
                                              uniform_part_weight=flags["uniform_part_weight"],
                                              coordinate_scale=float(model.coordinate_scale))
+    texture = None
+    if texture_size is not None:
+        texture = bake_texture(model, pose_to_camera, vertices, triangles, model_input, size=texture_size, color=texture_color)
     return RiggedMesh(vertices, triangles, joints, weights, kept, pose_to_camera.detach().float().clone(),
-                      bone_length.detach().float().reshape(1, -1, 1).clone(), colors, labels)
+                      bone_length.detach().float().reshape(1, -1, 1).clone(), colors, labels, texture)
 
 
 @torch.no_grad()
@@ -315,13 +402,41 @@ def _quaternion(R):
     return q
 
 
-def export_glb(rig: RiggedMesh, path: str) -> None:
+def _png_rgba(pixels) -> bytes:
+    """(H, W, 4) uint8 -> the bytes of an 8-bit RGBA PNG (zlib and struct only; no filtering)"""
+    import struct
+    import zlib
+    import numpy as np
+    h, w = pixels.shape[:2]
+    rows = np.zeros((h, 1 + 4 * w), np.uint8)
+    rows[:, 1:] = pixels.reshape(h, 4 * w)
+
+    def chunk(kind: bytes, data: bytes) -> bytes:
+        return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xFFFFFFFF)
+
+    return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 6, 0, 0, 0))
+            + chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + chunk(b"IEND", b""))
+
+
+def export_glb(rig: RiggedMesh, path: str, texture: Optional[TextureAtlas] = None, clips: Optional[Dict] = None) -> None:
     """The rigged mesh as binary glTF 2.0 (standard library and numpy only): one mesh primitive with POSITION, optional
     COLOR_0 (float RGB), JOINTS_0 / WEIGHTS_0 and, at 8 influences, JOINTS_1 / WEIGHTS_1 (joints as unsigned bytes, an
     unused slot as joint 0 with weight 0), 32-bit indices; a flat skeleton of P joint nodes under one identity root, node
     k carrying the rest frame of part k as translation and rotation (its rest bone length in `extras`), and
     inverseBindMatrices = the inverses of the rest frames. A viewer that sets node k to (t_k, R_k, uniform scale
-    bone_length_k / rest bone_length_k) of another pose reproduces skin_mesh. No animation clips."""
+    bone_length_k / rest bone_length_k) of another pose reproduces skin_mesh.
+
+    With a texture (`texture`, else rig.texture: a TextureAtlas of this mesh) the primitive is de-indexed - 3 T vertices,
+    the attributes of each corner copied, indices 0 ... 3 T - 1 - and carries TEXCOORD_0 = atlas_uv instead of COLOR_0, one
+    material (baseColorTexture, metallicFactor 0, roughnessFactor 1), one sampler (LINEAR both ways, CLAMP_TO_EDGE both
+    ways) and the texture as a PNG embedded through a buffer view.
+
+    `clips`: name -> (times (F,) in seconds, pose_to_camera (F, P, 4, 4) part frames with UNSCALED translation, as
+    skin_mesh takes them, bone_length (F, P, 1) or (1, P, 1)). Each becomes an entry of `animations` with a translation, a
+    rotation and a scale sampler for every part node, interpolation LINEAR: the rotation keys are unit quaternions whose
+    sign follows the previous key (no key has a negative dot product with its predecessor), the scale is bone_length /
+    rest bone_length, uniform. A viewer that plays a clip shows skin_mesh of its poses at the keys. With neither a texture
+    nor clips the file is the one earlier versions wrote, byte for byte."""
     import json
     import struct
     import numpy as np
@@ -360,8 +475,20 @@ def export_glb(rig: RiggedMesh, path: str) -> None:
         return len(accessors) - 1
 
     FLOAT, UBYTE, UINT, ARRAY, ELEMENT = 5126, 5121, 5125, 34962, 34963
+    texture = rig.texture if texture is None else texture
+    if texture is not None:
+        if texture.num_triangles != len(f):
+            raise ValueError(f"export_glb: the atlas was baked for {texture.num_triangles} triangles, the mesh has {len(f)}")
+        pixels = _host(texture.texture, np.uint8)
+        if pixels.shape != (texture.size, texture.size, 4):
+            raise ValueError(f"export_glb takes a ({texture.size}, {texture.size}, 4) uint8 texture, got {pixels.shape}")
+        corner = f.reshape(-1)                             # every corner a vertex of its own: its triangle's UV
+        v, joints, weights = v[corner], joints[corner], weights[corner]
+        f = np.arange(len(corner), dtype=np.int64).reshape(-1, 3)
     attributes = {"POSITION": add(v, "VEC3", FLOAT, ARRAY, bounds=len(v) > 0)}
-    if rig.colors is not None:
+    if texture is not None:
+        attributes["TEXCOORD_0"] = add(atlas_uv(texture.num_triangles, texture.size).reshape(-1, 2), "VEC2", FLOAT, ARRAY)
+    elif rig.colors is not None:
         c = np.clip(np.nan_to_num(_host(rig.colors, np.float32).reshape(-1, 3), nan=0.0), 0, 1)
         if c.shape != v.shape:
             raise ValueError(f"export_glb takes ({len(v)}, 3) colors, got {c.shape}")
@@ -376,11 +503,50 @@ def export_glb(rig: RiggedMesh, path: str) -> None:
               "rotation": [float(np.float32(x)) for x in quat[k]], "extras": {"bone_length": float(bone[k])}} for k in range(P)]
     nodes.append({"name": "skeleton", "children": list(range(P))})
     nodes.append({"name": "mesh", "mesh": 0, "skin": 0})
+    primitive = {"attributes": attributes, "indices": indices, "mode": 4}
+    extra = {}
+    if texture is not None:
+        png = _png_rgba(pixels)
+        views.append({"buffer": 0, "byteOffset": sum(len(c) for c in chunks), "byteLength": len(png)})
+        chunks.append(png + b"\0" * (-len(png) % 4))
+        primitive["material"] = 0
+        extra.update(materials=[{"pbrMetallicRoughness": {"baseColorTexture": {"index": 0}, "metallicFactor": 0.0,
+                                                          "roughnessFactor": 1.0}}],
+                     textures=[{"sampler": 0, "source": 0}],
+                     samplers=[{"magFilter": 9729, "minFilter": 9729, "wrapS": 33071, "wrapT": 33071}],
+                     images=[{"bufferView": len(views) - 1, "mimeType": "image/png"}])
+    if clips:
+        animations = []
+        for name, (times, poses, lengths) in clips.items():
+            times = _host(times, np.float32).reshape(-1)
+            poses = _host(poses, np.float64)
+            F = len(times)
+            if F < 1 or poses.shape != (F, P, 4, 4):
+                raise ValueError(f"export_glb: clip {name!r} takes ({F}, {P}, 4, 4) poses for {F} >= 1 times, got {poses.shape}")
+            lengths = _host(lengths, np.float64)
+            if lengths.shape not in ((F, P, 1), (1, P, 1)):
+                raise ValueError(f"export_glb: clip {name!r} takes ({F}, {P}, 1) or (1, {P}, 1) bone lengths, got {lengths.shape}")
+            scale = np.broadcast_to(lengths[:, :, 0] / bone[None, :], (F, P))
+            q = np.stack([_quaternion(poses[i, :, :3, :3]) for i in range(F)])                 # (F, P, 4)
+            for i in range(1, F):                       # the shorter arc from key to key
+                flip = np.einsum("pk,pk->p", q[i], q[i - 1]) < 0
+                q[i, flip] = -q[i, flip]
+            clock = add(times.reshape(-1, 1), "SCALAR", FLOAT, bounds=True)
+            samplers, channels = [], []
+            for k in range(P):
+                keys = (("translation", poses[:, k, :3, 3].astype(np.float32), "VEC3"),
+                        ("rotation", q[:, k].astype(np.float32), "VEC4"),
+                        ("scale", np.repeat(scale[:, k, None], 3, axis=1).astype(np.float32), "VEC3"))
+                for what, values, kind in keys:
+                    samplers.append({"input": clock, "interpolation": "LINEAR", "output": add(values, kind, FLOAT)})
+                    channels.append({"sampler": len(samplers) - 1, "target": {"node": k, "path": what}})
+            animations.append({"name": str(name), "samplers": samplers, "channels": channels})
+        extra["animations"] = animations
     doc = {"asset": {"version": "2.0", "generator": "enarf_gan_amd export_glb"}, "scene": 0,
            "scenes": [{"nodes": [P, P + 1]}], "nodes": nodes,
-           "meshes": [{"primitives": [{"attributes": attributes, "indices": indices, "mode": 4}]}],
+           "meshes": [{"primitives": [primitive]}],
            "skins": [{"joints": list(range(P)), "inverseBindMatrices": ibm, "skeleton": P}],
-           "buffers": [{"byteLength": sum(len(c) for c in chunks)}], "bufferViews": views, "accessors": accessors}
+           "buffers": [{"byteLength": sum(len(c) for c in chunks)}], "bufferViews": views, "accessors": accessors, **extra}
     text = json.dumps(doc, separators=(",", ":")).encode("utf-8")
     text += b" " * (-len(text) % 4)
     binary = b"".join(chunks)
@@ -453,6 +619,24 @@ def paint_mesh(vertices: torch.Tensor, triangles: torch.Tensor, intrinsics, img_
     fragments = rasterize_mesh(vertices, triangles, intrinsics, img_size, render_size)
     painted = ops.shade_fragments(fragments.pix_to_face, fragments.bary, fragments.normals, vertices, triangles,
                                   vertex_colors=vertex_colors, vertex_labels=vertex_labels, palette=palette, lit=lit)
+    return fragments, painted
+
+
+def paint_textured_mesh(vertices: torch.Tensor, triangles: torch.Tensor, atlas: TextureAtlas, intrinsics, img_size: int,
+                        render_size: int = 512, lit: bool = True, use_float: bool = False):
+    """The mesh drawn with its texture atlas: rasterize_mesh, then ops.shade_textured on its fragment buffers
+    (libenarf_bake.so, one launch more), with no host synchronisation. Returns what paint_mesh returns: (the
+    RasterizedMesh, the namedtuple (image (R, R, 3) uint8, albedo, shaded (R, R, 3) fp32)). The albedo is one bilinear tap
+    of atlas.texture (of atlas.texture_f32 with `use_float`); the mesh may be posed (skin_mesh), the triangles are the
+    atlas's. No CPU fallback."""
+    if atlas.num_triangles != triangles.shape[0]:
+        raise ValueError(f"paint_textured_mesh: the atlas was baked for {atlas.num_triangles} triangles, the mesh has "
+                         f"{triangles.shape[0]}")
+    if use_float and atlas.texture_f32 is None:
+        raise ValueError("paint_textured_mesh: use_float takes an atlas baked with want_float=True")
+    fragments = rasterize_mesh(vertices, triangles, intrinsics, img_size, render_size)
+    painted = ops.shade_textured(fragments.pix_to_face, fragments.bary, fragments.normals, vertices, triangles,
+                                 atlas.texture_f32 if use_float else atlas.texture, lit=lit)
     return fragments, painted
 
 

@@ -204,13 +204,69 @@ class TriNARFGenerator(_RendererShell):
         return frames
 
     def extract_rigged_mesh(self, pose_to_camera, z, bone_length, voxel_size=0.003, mesh_th=15, truncation_psi=0.4,
-                            max_influences=4, return_colors=False, return_part_labels=False):
+                            max_influences=4, return_colors=False, return_part_labels=False, texture_size=None,
+                            texture_color="field"):
         """extract_mesh in the rest pose pose_to_camera, bound to the model's parts: a RiggedMesh (mesh_rendering) with
         joints and weights (V, max_influences = 4 or 8) from one launch of the HIP skin-weight kernel, ready for
-        render_mesh_animation, mesh_rendering.skin_mesh and mesh_rendering.export_glb; one sample, as extract_mesh."""
+        render_mesh_animation, mesh_rendering.skin_mesh and mesh_rendering.export_glb; one sample, as extract_mesh.
+        `texture_size` adds rig.texture, the texture atlas of the mesh baked in this pose in `texture_color` ("field" or
+        "parts"), for render_textured_mesh_animation and a textured export_glb."""
         z_nerf, z_render, _ = self._latent_parts(z)
         return self.nerf.extract_rigged_mesh(pose_to_camera, z_nerf, z_render, bone_length, voxel_size, mesh_th,
-                                             truncation_psi, max_influences, return_colors, return_part_labels)
+                                             truncation_psi, max_influences, return_colors, return_part_labels,
+                                             texture_size, texture_color)
+
+    def bake_texture(self, pose_to_camera, z, bone_length, vertices, triangles, truncation_psi=0.4, size=1024,
+                     color="field", palette=None, color_fn=None, want_float=False):
+        """The texture atlas of a mesh extract_mesh returned for the same arguments: a TextureAtlas (mesh_rendering) of
+        size x size texels holding the field's colour (color="field") or the part colours (color="parts") at the surface
+        point of every texel, from the HIP bake kernels and one query launch a band of rows; one sample."""
+        z_nerf, z_render, _ = self._latent_parts(z)
+        return self.nerf.bake_texture(pose_to_camera, z_nerf, z_render, bone_length, vertices, triangles, truncation_psi,
+                                      size, color, palette, color_fn, want_float)
+
+    def render_textured_mesh(self, pose_to_camera, intrinsics, z, bone_length, voxel_size=0.01, mesh_th=15,
+                             truncation_psi=0.4, texture_size=1024, color="field", lit=True):
+        """render_colored_mesh with the colour in a texture atlas: a mesh coarse enough for other tools (voxel 0.01) keeps
+        the field's colour detail. (image (512, 512, 3) uint8 numpy, (vertices, triangles, the TextureAtlas)); one sample."""
+        z_nerf, z_render, _ = self._latent_parts(z)
+        return self.nerf.render_textured_mesh(pose_to_camera, intrinsics, z_nerf, z_render, bone_length, voxel_size,
+                                              mesh_th, truncation_psi, self.size, texture_size, color, lit)
+
+    def render_textured_mesh_animation(self, rig, key_poses, bone_length, intrinsics, num=100, loop=True, orbit=None,
+                                       lit=True, render_size=512, frames_per_batch=8):
+        """render_mesh_animation drawn with rig.texture (a rig from extract_rigged_mesh(texture_size=...)): (frames
+        (num, R, R, 3) uint8, poses (num, J, 4, 4) in key_poses' dtype), device tensors, with no host synchronisation
+        inside. One interpolate_pose launch; the frames posed frames_per_batch at a time by one skin_pose launch; every
+        frame one rasterize_mesh and one shade_textured: the texture was baked once, in the rest pose, and moves with the
+        triangles. The bytes do not depend on frames_per_batch."""
+        from .. import ops
+        from ..libraries.NARF.mesh_rendering import rasterize_mesh, skin_mesh
+        if rig.texture is None:
+            raise ValueError("render_textured_mesh_animation takes a rig extracted with texture_size=...")
+        if rig.texture.num_triangles != rig.triangles.shape[0]:
+            raise ValueError(f"render_textured_mesh_animation: the atlas was baked for {rig.texture.num_triangles} triangles, "
+                             f"the rig has {rig.triangles.shape[0]}")
+        if bone_length.shape[0] != 1:
+            raise AssertionError("render_textured_mesh_animation takes one identity: bone_length of batch 1")
+        per = int(frames_per_batch)
+        if per < 1:
+            raise ValueError(f"render_textured_mesh_animation: frames_per_batch {frames_per_batch} < 1")
+        nerf, R = self.nerf, int(render_size)
+        with torch.no_grad():
+            poses, poses32 = ops.interpolate_pose(key_poses, nerf.parent_id, num, loop, orbit, return_f32=True)
+            dev, n_frames, V = poses.device, poses.shape[0], rig.vertices.shape[0]
+            frames = torch.empty((n_frames, R, R, 3), dtype=torch.uint8, device=dev)
+            posed = torch.empty((min(per, n_frames), V, 3), dtype=torch.float32, device=dev)
+            for a in range(0, n_frames, per):
+                b = min(a + per, n_frames)
+                pose_parts, bl = nerf.transform_pose(poses32[a:b], bone_length.float().expand(b - a, -1, -1))
+                skin_mesh(nerf, rig, pose_parts, bl, out=posed[:b - a])
+                for i in range(a, b):
+                    f = rasterize_mesh(posed[i - a], rig.triangles, intrinsics, self.size, R)
+                    frames[i] = ops.shade_textured(f.pix_to_face, f.bary, f.normals, posed[i - a], rig.triangles,
+                                                   rig.texture.texture, lit=lit).image
+        return frames, poses
 
     def render_mesh_animation(self, rig, key_poses, bone_length, intrinsics, num=100, loop=True, orbit=None, color="field",
                               lit=True, render_size=512, frames_per_batch=8):

@@ -367,14 +367,40 @@ class TriPlaneNARF(nn.Module):
         return extract_mesh(self, pose_parts, center, voxel_size, mesh_th, model_input, return_part_labels, return_colors)
 
     def extract_rigged_mesh(self, pose_to_camera, z, z_rend, bone_length, voxel_size=0.003, mesh_th=15, truncation_psi=0.4,
-                            max_influences=4, return_colors=False, return_part_labels=False):
+                            max_influences=4, return_colors=False, return_part_labels=False, texture_size=None,
+                            texture_color="field"):
         """extract_mesh in the rest pose pose_to_camera (1, J, 4, 4), bound to the parts: the RiggedMesh of
         mesh_rendering.extract_rigged_mesh (vertices, triangles, joints and weights (V, max_influences), kept_mass, the
-        rest part frames and bone lengths, optional colours and labels). One skin-weight launch more than extract_mesh."""
+        rest part frames and bone lengths, optional colours and labels). One skin-weight launch more than extract_mesh;
+        `texture_size` adds the texture atlas of the mesh, baked in this pose in `texture_color`."""
         from ..libraries.NARF.mesh_rendering import extract_rigged_mesh
         center, pose_parts, model_input = self._mesh_inputs(pose_to_camera, z, z_rend, bone_length, truncation_psi)
         return extract_rigged_mesh(self, pose_parts, center, voxel_size, mesh_th, model_input, max_influences, return_colors,
-                                   return_part_labels)
+                                   return_part_labels, texture_size, texture_color)
+
+    def bake_texture(self, pose_to_camera, z, z_rend, bone_length, vertices, triangles, truncation_psi=0.4, size=1024,
+                     color="field", palette=None, color_fn=None, want_float=False):
+        """The texture atlas of a mesh extracted in the pose pose_to_camera (1, J, 4, 4): the TextureAtlas of
+        mesh_rendering.bake_texture, size x size texels, every texel a triangle owns holding the radiance field's colour
+        (color="field") or its part's palette colour (color="parts") at the texel's surface point; one sample."""
+        from ..libraries.NARF.mesh_rendering import bake_texture
+        _, pose_parts, model_input = self._mesh_inputs(pose_to_camera, z, z_rend, bone_length, truncation_psi)
+        return bake_texture(self, pose_parts, vertices, triangles, model_input, size, color, palette, color_fn, want_float)
+
+    def render_textured_mesh(self, pose_to_camera, intrinsics, z, z_rend, bone_length, voxel_size=0.01, mesh_th=15,
+                             truncation_psi=0.4, img_size=128, texture_size=1024, color="field", lit=True):
+        """render_colored_mesh with the colour in a texture instead of on the vertices: extract_mesh -> bake_texture ->
+        paint_textured_mesh (HIP rasteriser, HIP textured shading, 512 x 512), one host copy of the finished image. The
+        colour resolution is the atlas's, not the mesh's: a coarse mesh keeps the field's detail. Returns (image
+        (512, 512, 3) uint8 numpy, (vertices, triangles, the TextureAtlas)); one sample."""
+        from ..libraries.NARF.mesh_rendering import bake_texture, extract_mesh, paint_textured_mesh
+        if color not in ("field", "parts"):
+            raise ValueError(f"color is 'field' (the radiance field's colour) or 'parts' (the part labels), got {color!r}")
+        center, pose_parts, model_input = self._mesh_inputs(pose_to_camera, z, z_rend, bone_length, truncation_psi)
+        vertices, triangles = extract_mesh(self, pose_parts, center, voxel_size, mesh_th, model_input)
+        atlas = bake_texture(self, pose_parts, vertices, triangles, model_input, texture_size, color)
+        _, painted = paint_textured_mesh(vertices, triangles, atlas, intrinsics, img_size, lit=lit)
+        return painted.image.cpu().numpy(), (vertices, triangles, atlas)
 
     def part_labels(self, points, pose_to_camera, z, bone_length, truncation_psi=1, points_last=False,
                     return_valid_bits=False):

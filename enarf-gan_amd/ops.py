@@ -944,6 +944,54 @@ def shade_fragments(pix_to_face: torch.Tensor, bary: torch.Tensor, normals: torc
                                       lit, background, neutral)
 
 
+# ------------------------------------------------------------------------------------------------- textured meshes
+def bake_layout(T: int, size: int):
+    """The texture atlas of T triangles in `size` x `size` texels: BakeLayout(cell, cells_per_row, capacity). Triangles are
+    packed in pairs into square cells of `cell` texels a side, the largest integer >= 6 with 2 (size // cell)^2 >= T (the
+    layout is a function of T and size alone, include/enarf_bake.h). ValueError for 6 <= size <= 8192 or 0 <= T < 2^31
+    violated, NotImplementedError when size is too small for T (the message says how large it must be). Pure host
+    arithmetic: no device, no library."""
+    from . import _bake_lib
+    return _bake_lib.bake_layout(T, size)
+
+
+def bake_points(vertices: torch.Tensor, triangles: torch.Tensor, size: int, rows=None):
+    """The surface point of every texel of a mesh's atlas, in one launch of libenarf_bake.so: the namedtuple (points
+    (3, rows size) fp32 - three planes, the layout query_fwd takes -, texel_face (rows, size) int32 - the triangle that
+    owns the texel, -1 for an empty one, whose point is (0, 0, 0)). vertices (V, 3) fp32, triangles (T, 3) int64; `rows` =
+    (first, stop) restricts the call to a band of atlas rows (all rows by default), so that a large atlas is baked band
+    by band. A triangle naming a vertex outside [0, V) owns nothing. Computed in fp64 from the fp32 inputs and rounded
+    once; bit-identical from run to run, nothing synchronises. ValueError for shapes, dtypes or devices it does not take,
+    NotImplementedError for an atlas too small for the mesh."""
+    from . import _bake_lib
+    return _bake_lib.bake_points(vertices, triangles, size, rows)
+
+
+def bake_resolve(texel_face: torch.Tensor, *, color: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None,
+                 palette: Optional[torch.Tensor] = None, fill=0.0, neutral=0.5, want_float: bool = False,
+                 unit: bool = False, out=None):
+    """The colours or labels found at bake_points' points to the texture, in one launch of libenarf_bake.so: the
+    namedtuple (texture (rows, size, 4) uint8, texture_f32 (rows, size, 3) fp32 or None). texel_face (rows, size) int32
+    and exactly one of color (3, rows size) fp32 as query_fwd returns it, in [-1, 1] and mapped by (x + 1) / 2 (`unit`:
+    already in [0, 1]), or labels (rows size) int32 with palette (P, 3) fp32 in [0, 1] (`neutral` for a label outside
+    [0, P)). rgb = floor(255 clamp(v, 0, 1)), a NaN giving 0, alpha 255; an empty texel takes `fill` and alpha 0.
+    `want_float` adds the unquantised fp32 texture; `out` = (texture, texture_f32 or None) writes into given tensors."""
+    from . import _bake_lib
+    return _bake_lib.bake_resolve(texel_face, color, labels, palette, fill, neutral, want_float, unit, out)
+
+
+def shade_textured(pix_to_face: torch.Tensor, bary: torch.Tensor, normals: torch.Tensor, vertices: torch.Tensor,
+                   triangles: torch.Tensor, texture: torch.Tensor, *, lit: bool = True, background=1.0):
+    """shade_fragments with the albedo read from a baked texture, in one launch of libenarf_bake.so: the namedtuple (image
+    (R, R, 3) uint8, albedo (R, R, 3) fp32, shaded (R, R, 3) fp32). The fragment buffers as rasterize_mesh returns them,
+    the mesh they were rasterised from, and its texture: (A, A, 4) uint8 (alpha ignored) or (A, A, 3) fp32. The uv of a
+    pixel is the barycentric mix of its face's corner positions in the atlas (from the layout, nothing stored), the
+    albedo one bilinear tap there, clamped to the edge; the lighting is shade_fragments'. Bit-identical from run to run,
+    nothing synchronises."""
+    from . import _bake_lib
+    return _bake_lib.shade_textured(pix_to_face, bary, normals, vertices, triangles, texture, lit, background)
+
+
 # ------------------------------------------------------------------------------------------------- rigged meshes
 def skin_weights(vertices: torch.Tensor, parts_rest: torch.Tensor, canonical_pose: torch.Tensor, tri_plane: torch.Tensor, *,
                  max_influences: int = 4, clamp_mask: bool = False, uniform_part_weight: bool = False,

@@ -25,7 +25,10 @@ inverse depth between `--depth-range` - from the disparity of each frame (ops.ge
 `--skinned-mesh field|parts|white` extracts the mesh of the first key once, binds it to the model's parts
 (extract_rigged_mesh: `--influences` 4 or 8 a vertex) and moves it through the key poses by linear-blend skinning
 (render_mesh_animation: one skin_pose launch a chunk, HIP rasteriser and deferred shading per frame); `--export-glb PATH`
-writes that rig as a skinned binary glTF (mesh_rendering.export_glb), with or without --skinned-mesh."""
+writes that rig as a skinned binary glTF (mesh_rendering.export_glb), with or without --skinned-mesh. `--texture-size N`
+bakes the field's colour into an N x N texture atlas of that mesh (libenarf_bake.so): the glTF then carries the texture in
+place of the vertex colours, and `--skinned-mesh texture` draws the posed mesh with it; `--clip` writes the interpolated
+sequence into the glTF as an animation clip."""
 import argparse
 import math
 import os
@@ -59,10 +62,16 @@ def main():
     ap.add_argument("--depth-range", default="1.0,5.0", help="--geometry depth: near,far in the poses' units")
     ap.add_argument("--mesh-turntable", choices=["field", "parts"], default=None,
                     help="a turntable of the first key's coloured mesh in place of the march")
-    ap.add_argument("--skinned-mesh", choices=["field", "parts", "white"], default=None,
+    ap.add_argument("--skinned-mesh", choices=["field", "parts", "white", "texture"], default=None,
                     help="the first key's mesh, rigged once and posed per frame, in place of the march")
     ap.add_argument("--influences", type=int, choices=[4, 8], default=4, help="skinned mesh: parts a vertex is bound to")
     ap.add_argument("--export-glb", default=None, help="write the rigged mesh of the first key as binary glTF to this path")
+    ap.add_argument("--texture-size", type=int, default=None,
+                    help="bake the field's colour into a texture atlas of this size: --export-glb embeds it in place of the "
+                         "vertex colours; --skinned-mesh texture draws with it (1024 when not given)")
+    ap.add_argument("--clip", action="store_true",
+                    help="--export-glb: write the interpolated sequence into the file as an animation clip")
+    ap.add_argument("--fps", type=float, default=24.0, help="--clip: key frames a second")
     ap.add_argument("--voxel-size", type=float, default=0.003, help="mesh turntable: the density sweep's voxel")
     ap.add_argument("--mesh-th", type=float, default=15.0, help="mesh turntable: the density threshold")
     ap.add_argument("--unlit", action="store_true", help="mesh turntable: the colour itself, without the Phong terms")
@@ -97,16 +106,30 @@ def main():
     if args.orbit_turns:
         orbit = torch.arange(args.num, dtype=torch.float64, device=dev) * (2 * math.pi * args.orbit_turns / args.num)
     rig = None
+    textured = args.skinned_mesh == "texture"
     if args.skinned_mesh or args.export_glb:
         rig = gen.extract_rigged_mesh(key_poses[:1].float(), z, bone_length, voxel_size=args.voxel_size, mesh_th=args.mesh_th,
                                       truncation_psi=args.truncation_psi, max_influences=args.influences,
-                                      return_colors=True, return_part_labels=True)
+                                      return_colors=True, return_part_labels=True,
+                                      texture_size=1024 if textured and args.texture_size is None else args.texture_size)
         if args.export_glb:
+            from enarf_gan_amd import ops
             from enarf_gan_amd.libraries.NARF.mesh_rendering import export_glb
-            export_glb(rig, args.export_glb)
+            clips = None
+            if args.clip:
+                poses = ops.interpolate_pose(key_poses, gen.nerf.parent_id, args.num, not args.no_loop, orbit)
+                part_poses, part_lengths = gen.nerf.transform_pose(poses.float(), bone_length.expand(poses.shape[0], -1, -1))
+                clips = {"sequence": (np.arange(poses.shape[0]) / args.fps, part_poses, part_lengths)}
+            export_glb(rig, args.export_glb, clips=clips)
             print(f"{args.export_glb}: {len(rig.vertices)} vertices, {len(rig.triangles)} triangles, "
-                  f"{rig.joints.shape[1]} influences", file=sys.stderr)
-    if args.skinned_mesh:
+                  f"{rig.joints.shape[1]} influences"
+                  + (f", a {rig.texture.size} x {rig.texture.size} texture (cell {rig.texture.cell})" if rig.texture else "")
+                  + (f", a clip of {len(clips['sequence'][0])} keys" if clips else ""), file=sys.stderr)
+    if textured:
+        frames, _ = gen.render_textured_mesh_animation(rig, key_poses, bone_length, intrinsics, num=args.num,
+                                                       loop=not args.no_loop, orbit=orbit, lit=not args.unlit,
+                                                       render_size=args.render_size, frames_per_batch=args.frames_per_batch)
+    elif args.skinned_mesh:
         frames, _ = gen.render_mesh_animation(rig, key_poses, bone_length, intrinsics, num=args.num, loop=not args.no_loop,
                                               orbit=orbit, color=None if args.skinned_mesh == "white" else args.skinned_mesh,
                                               lit=not args.unlit, render_size=args.render_size,

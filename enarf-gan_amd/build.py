@@ -40,6 +40,7 @@ SIDE_LIBRARIES = {
     "seg": (["enarf_seg.hip"], "enarf_seg.h"),             # part labels of sample points and the semantic map of a frame
     "paint": (["enarf_paint.hip"], "enarf_paint.h"),       # deferred shading of a rasterised mesh: vertex colours, part labels
     "bake": (["enarf_bake.hip"], "enarf_bake.h"),          # the texture atlas of a mesh: texel points, RGBA8 texture, textured shade
+    "simp": (["enarf_simp.hip"], "enarf_simp.h"),          # mesh simplification: vertex clustering with quadric placement
     "geom": (["enarf_geom.hip"], "enarf_geom.h"),          # depth, point and normal maps of a march, running depth error
     "pgrad": (["enarf_pgrad.hip"], "enarf_pgrad.h"),       # the query's gradient for the sample points and the part frames
     "scene": (["enarf_scene.hip"], "enarf_scene.h"),       # several avatars marched on the same rays, composed into one image

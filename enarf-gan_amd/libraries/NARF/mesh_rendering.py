@@ -14,6 +14,9 @@ to the model's parts (a `RiggedMesh`: extract_mesh plus one skin-weight launch o
 linear-blend skinning without a new extraction, and `export_glb` writes it as a skinned binary glTF. `bake_texture` gives a
 mesh a texture atlas of the field's colour (a `TextureAtlas`: libenarf_bake.so for the texel points and the texture, the
 query kernel for the colours), `paint_textured_mesh` draws the mesh with it, and `export_glb` embeds it and animation clips.
+`simplify_mesh` makes a finely extracted mesh small (vertex clustering with quadric placement, libenarf_simp.so);
+`simplify_cell` on extract_mesh and extract_rigged_mesh does it straight after marching cubes, so that labels, colours, skin
+weights and the texture are computed on the small mesh.
 """
 from __future__ import annotations
 
@@ -146,24 +149,81 @@ def vertex_colors(model, pose_to_camera: torch.Tensor, vertices: torch.Tensor, m
 
 @torch.no_grad()
 def extract_mesh(model, pose_to_camera: torch.Tensor, center: torch.Tensor, voxel_size: float = 0.003, mesh_th: float = 15,
-                 model_input: Dict = {}, return_part_labels: bool = False, return_colors: bool = False):
+                 model_input: Dict = {}, return_part_labels: bool = False, return_colors: bool = False,
+                 simplify_cell: Optional[float] = None):
     """create_mesh (mesh_rendering.py:50-81) on the device: density_volume -> marching_cubes -> the reference's
     transform (vertices - cube) * voxel_size + center, in fp32. Returns (vertices (V, 3), triangles (T, 3) int64) on
     pose_to_camera's device. `return_part_labels` adds (V,) int32: the part that owns each vertex (-1: none), one
     point_part_labels launch over the vertex array; `return_colors` adds (V, 3) fp32 in [0, 1], the field's colour at
-    each vertex (vertex_colors, one query launch); with both the result is (vertices, triangles, labels, colors)."""
+    each vertex (vertex_colors, one query launch); with both the result is (vertices, triangles, labels, colors).
+    `simplify_cell` = h simplifies the mesh straight after the transform (ops.simplify_mesh(vertices, triangles, h):
+    extract fine, cluster to cells of h camera units); labels and colours are then those of the simplified vertices."""
     if pose_to_camera.device.type != "cuda":
         raise _mesh_lib.EnarfHipError("extract_mesh runs on the device (there is no CPU fallback)")
     density = density_volume(model, pose_to_camera, center, voxel_size, model_input)
     cube = int(1 / voxel_size)
     vertices, triangles = marching_cubes(density, mesh_th)
     vertices = (vertices - cube) * voxel_size + center.to(vertices.device).float()[:, :, 0]
+    if simplify_cell is not None:
+        vertices, triangles = ops.simplify_mesh(vertices, triangles, simplify_cell)[:2]
     out = (vertices, triangles)
     if return_part_labels:
         out += (point_part_labels(model, pose_to_camera, vertices, model_input, points_last=True)[0][0],)
     if return_colors:
         out += (vertex_colors(model, pose_to_camera, vertices, model_input),)
     return out
+
+
+def simplify_mesh(vertices: torch.Tensor, triangles: torch.Tensor, cell: Optional[float] = None,
+                  target_triangles: Optional[int] = None, origin=None, placement: str = "quadric", reg: float = 1e-3,
+                  max_runs: int = 12):
+    """A finely extracted mesh made small: ops.simplify_mesh (uniform-grid vertex clustering, every new vertex placed by
+    the quadric of the fine triangles that touch its cell; libenarf_simp.so) at the cell size `cell`, or at the finest cell
+    found for which the result has at most `target_triangles` triangles. Exactly one of the two must be given. Returns
+    the named tuple of ops.simplify_mesh, (vertices (C, 3) fp32, triangles (T', 3) int64, vertex_cluster (V,) int32,
+    cluster_size (C,) int32).
+
+    With `target_triangles` the cell is bisected over at most `max_runs` (12) runs of ops.simplify_mesh: the coarse end
+    starts at the bounding-box diagonal (one cluster, no triangle: always within the target), the fine end at 0, each run
+    tries the midpoint and keeps it as the coarse end when T' <= target, as the fine end otherwise; the mesh of the last
+    coarse end is returned (run 1 is the diagonal itself). simplify_steps gives every run's (cell, T').
+
+    Clustering does not preserve topology: surfaces nearer than a cell can merge and edges can become non-manifold.
+    Attributes are not carried across: evaluate labels, colours, skin weights and the texture at the new vertices."""
+    if (cell is None) == (target_triangles is None):
+        raise ValueError("simplify_mesh takes exactly one of cell and target_triangles, got " +
+                         ("both" if cell is not None else "neither"))
+    if cell is not None:
+        return ops.simplify_mesh(vertices, triangles, cell, origin=origin, placement=placement, reg=reg)
+    return simplify_steps(vertices, triangles, target_triangles, origin, placement, reg, max_runs)[0]
+
+
+def simplify_steps(vertices: torch.Tensor, triangles: torch.Tensor, target_triangles: int, origin=None,
+                   placement: str = "quadric", reg: float = 1e-3, max_runs: int = 12):
+    """The bisection of simplify_mesh(target_triangles=...): (the mesh returned, [(cell, T') of every run, in order])"""
+    target = int(target_triangles)
+    if target < 0 or int(max_runs) < 1:
+        raise ValueError(f"simplify_mesh: target_triangles >= 0 and max_runs >= 1, got {target_triangles!r}, {max_runs!r}")
+    run = lambda h: ops.simplify_mesh(vertices, triangles, h, origin=origin, placement=placement, reg=reg)
+    if vertices.shape[0] == 0:
+        return run(1.0), []
+    extent = (vertices.amax(0) - vertices.amin(0)).double()
+    coarse = max(float(extent.square().sum().sqrt()), 1e-30) * 1.0001          # above the diagonal: every vertex in one cell
+    fine, best, steps = 0.0, run(coarse), []
+    steps.append((coarse, best.triangles.shape[0]))
+    for _ in range(int(max_runs) - 1):
+        h = 0.5 * (fine + coarse)
+        try:
+            got = run(h)
+        except NotImplementedError:            # more than 2^21 cells an axis: finer than any useful target
+            fine = h
+            continue
+        steps.append((h, got.triangles.shape[0]))
+        if got.triangles.shape[0] <= target:
+            coarse, best = h, got
+        else:
+            fine = h
+    return best, steps
 
 
 @dataclasses.dataclass
@@ -279,14 +339,16 @@ def _mask_tri_plane(model, model_input: Dict) -> torch.Tensor:
 def extract_rigged_mesh(model, pose_to_camera: torch.Tensor, center: torch.Tensor, voxel_size: float = 0.003,
                         mesh_th: float = 15, model_input: Dict = {}, max_influences: int = 4, return_colors: bool = False,
                         return_part_labels: bool = False, texture_size: Optional[int] = None,
-                        texture_color: str = "field") -> RiggedMesh:
+                        texture_color: str = "field", simplify_cell: Optional[float] = None) -> RiggedMesh:
     """extract_mesh in the pose pose_to_camera (1, P, 4, 4) - the rest pose of the rig - plus one ops.skin_weights launch
     over the vertex array: every vertex bound to the max_influences (4 or 8) parts of the largest part probability among
     the parts whose cube contains it. `return_colors` and `return_part_labels` fill the record's colors and labels as
     extract_mesh returns them; `texture_size` fills its texture: bake_texture of the mesh in this pose, in `texture_color`
-    ("field" or "parts"). The mesh is posed by skin_mesh and written out by export_glb."""
+    ("field" or "parts"). The mesh is posed by skin_mesh and written out by export_glb. `simplify_cell` as in extract_mesh:
+    the skin weights, colours, labels and the texture are those of the simplified mesh."""
     from ..NeRF.rendering import _parts_from_part_poses
-    got = extract_mesh(model, pose_to_camera, center, voxel_size, mesh_th, model_input, return_part_labels, return_colors)
+    got = extract_mesh(model, pose_to_camera, center, voxel_size, mesh_th, model_input, return_part_labels, return_colors,
+                       simplify_cell)
     vertices, triangles, extra = got[0], got[1], list(got[2:])
     labels = extra.pop(0) if return_part_labels else None
     colors = extra.pop(0) if return_colors else None

@@ -130,13 +130,15 @@ class TriNARFGenerator(_RendererShell):
         return self.nerf.density_volume(pose_to_camera, z_nerf, z_render, bone_length, voxel_size, truncation_psi)
 
     def extract_mesh(self, pose_to_camera, z, bone_length, voxel_size=0.003, mesh_th=15, truncation_psi=0.4,
-                     return_part_labels=False, return_colors=False):
+                     return_part_labels=False, return_colors=False, simplify_cell=None):
         """create_mesh's (vertices, triangles) built on the device (HIP marching cubes); one sample, as create_mesh.
         `return_part_labels` adds the (V,) int32 part that owns each vertex, `return_colors` the (V, 3) fp32 colour of
-        the field at each vertex, in [0, 1] (after the labels when both are asked for)."""
+        the field at each vertex, in [0, 1] (after the labels when both are asked for). `simplify_cell` = h simplifies
+        the mesh to cells of h camera units straight after marching cubes (HIP vertex clustering with quadric placement):
+        extract fine, keep few triangles; labels and colours are then those of the simplified vertices."""
         z_nerf, z_render, _ = self._latent_parts(z)
         return self.nerf.extract_mesh(pose_to_camera, z_nerf, z_render, bone_length, voxel_size, mesh_th, truncation_psi,
-                                      return_part_labels, return_colors)
+                                      return_part_labels, return_colors, simplify_cell)
 
     @torch.no_grad()
     def render_part_map(self, pose_to_camera, bone_length, z, inv_intrinsics, truncation_psi=1):
@@ -182,8 +184,8 @@ class TriNARFGenerator(_RendererShell):
                                              mesh_th, truncation_psi, self.size, color, lit)
 
     def render_mesh_turntable(self, pose_to_camera, intrinsics, z, bone_length, angles, voxel_size=0.003, mesh_th=15,
-                              truncation_psi=0.4, color="field", lit=True, render_size=512):
-        """The coloured mesh of render_colored_mesh on a turntable: (num, R, R, 3) uint8 frames on the device, frame i
+                              truncation_psi=0.4, color="field", lit=True, render_size=512, simplify_cell=None):
+        """The coloured mesh of render_colored_mesh (simplified to cells of `simplify_cell` when given) on a turntable: (num, R, R, 3) uint8 frames on the device, frame i
         the mesh turned by angles[i] about the y axis through the mean joint translation (rotate_mesh_by_angle). The
         mesh and its colours or labels are extracted once; every angle is one rotate_mesh_by_angle, one rasterize_mesh
         and one shade_fragments, with no host synchronisation inside. angles: num numbers or a (num,) tensor."""
@@ -192,7 +194,7 @@ class TriNARFGenerator(_RendererShell):
         from ..libraries.NARF.pose_utils import rotate_mesh_by_angle
         z_nerf, z_render, _ = self._latent_parts(z)
         vertices, triangles, _, how = self.nerf._colored_mesh(pose_to_camera, z_nerf, z_render, bone_length, voxel_size,
-                                                              mesh_th, truncation_psi, color)
+                                                              mesh_th, truncation_psi, color, simplify_cell)
         dev, R = vertices.device, int(render_size)
         angles = torch.as_tensor(angles).to(device=dev, dtype=torch.float32).reshape(-1)
         frames = torch.empty((angles.shape[0], R, R, 3), dtype=torch.uint8, device=dev)
@@ -205,8 +207,8 @@ class TriNARFGenerator(_RendererShell):
 
     def extract_rigged_mesh(self, pose_to_camera, z, bone_length, voxel_size=0.003, mesh_th=15, truncation_psi=0.4,
                             max_influences=4, return_colors=False, return_part_labels=False, texture_size=None,
-                            texture_color="field"):
-        """extract_mesh in the rest pose pose_to_camera, bound to the model's parts: a RiggedMesh (mesh_rendering) with
+                            texture_color="field", simplify_cell=None):
+        """extract_mesh (with its `simplify_cell`) in the rest pose pose_to_camera, bound to the model's parts: a RiggedMesh (mesh_rendering) with
         joints and weights (V, max_influences = 4 or 8) from one launch of the HIP skin-weight kernel, ready for
         render_mesh_animation, mesh_rendering.skin_mesh and mesh_rendering.export_glb; one sample, as extract_mesh.
         `texture_size` adds rig.texture, the texture atlas of the mesh baked in this pose in `texture_color` ("field" or
@@ -214,7 +216,7 @@ class TriNARFGenerator(_RendererShell):
         z_nerf, z_render, _ = self._latent_parts(z)
         return self.nerf.extract_rigged_mesh(pose_to_camera, z_nerf, z_render, bone_length, voxel_size, mesh_th,
                                              truncation_psi, max_influences, return_colors, return_part_labels,
-                                             texture_size, texture_color)
+                                             texture_size, texture_color, simplify_cell)
 
     def bake_texture(self, pose_to_camera, z, bone_length, vertices, triangles, truncation_psi=0.4, size=1024,
                      color="field", palette=None, color_fn=None, want_float=False):
@@ -226,12 +228,14 @@ class TriNARFGenerator(_RendererShell):
                                       size, color, palette, color_fn, want_float)
 
     def render_textured_mesh(self, pose_to_camera, intrinsics, z, bone_length, voxel_size=0.01, mesh_th=15,
-                             truncation_psi=0.4, texture_size=1024, color="field", lit=True):
+                             truncation_psi=0.4, texture_size=1024, color="field", lit=True, simplify_cell=None):
         """render_colored_mesh with the colour in a texture atlas: a mesh coarse enough for other tools (voxel 0.01) keeps
-        the field's colour detail. (image (512, 512, 3) uint8 numpy, (vertices, triangles, the TextureAtlas)); one sample."""
+        the field's colour detail. `simplify_cell` gets the coarse mesh from a fine extraction instead (a smaller
+        voxel_size, simplified to cells of simplify_cell). (image (512, 512, 3) uint8 numpy, (vertices, triangles, the
+        TextureAtlas)); one sample."""
         z_nerf, z_render, _ = self._latent_parts(z)
         return self.nerf.render_textured_mesh(pose_to_camera, intrinsics, z_nerf, z_render, bone_length, voxel_size,
-                                              mesh_th, truncation_psi, self.size, texture_size, color, lit)
+                                              mesh_th, truncation_psi, self.size, texture_size, color, lit, simplify_cell)
 
     def render_textured_mesh_animation(self, rig, key_poses, bone_length, intrinsics, num=100, loop=True, orbit=None,
                                        lit=True, render_size=512, frames_per_batch=8):

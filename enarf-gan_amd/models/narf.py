@@ -357,26 +357,28 @@ class TriPlaneNARF(nn.Module):
         return density_volume(self, pose_parts, center, voxel_size, model_input)
 
     def extract_mesh(self, pose_to_camera, z, z_rend, bone_length, voxel_size=0.003, mesh_th=15, truncation_psi=0.4,
-                     return_part_labels=False, return_colors=False):
+                     return_part_labels=False, return_colors=False, simplify_cell=None):
         """The mesh of render_mesh / create_mesh built on the device: density sweep -> HIP marching cubes -> the
         reference's transform (mesh_rendering.extract_mesh). Returns (vertices (V, 3), triangles (T, 3) int64) and, with
         `return_part_labels`, (V,) int32 labels: the part that owns each vertex; with `return_colors`, (V, 3) fp32 in
-        [0, 1]: the field's colour at each vertex (after the labels when both are asked for)."""
+        [0, 1]: the field's colour at each vertex (after the labels when both are asked for). `simplify_cell` = h
+        simplifies the mesh to cells of h straight after marching cubes (mesh_rendering.simplify_mesh)."""
         from ..libraries.NARF.mesh_rendering import extract_mesh
         center, pose_parts, model_input = self._mesh_inputs(pose_to_camera, z, z_rend, bone_length, truncation_psi)
-        return extract_mesh(self, pose_parts, center, voxel_size, mesh_th, model_input, return_part_labels, return_colors)
+        return extract_mesh(self, pose_parts, center, voxel_size, mesh_th, model_input, return_part_labels, return_colors,
+                            simplify_cell)
 
     def extract_rigged_mesh(self, pose_to_camera, z, z_rend, bone_length, voxel_size=0.003, mesh_th=15, truncation_psi=0.4,
                             max_influences=4, return_colors=False, return_part_labels=False, texture_size=None,
-                            texture_color="field"):
-        """extract_mesh in the rest pose pose_to_camera (1, J, 4, 4), bound to the parts: the RiggedMesh of
+                            texture_color="field", simplify_cell=None):
+        """extract_mesh (with its `simplify_cell`) in the rest pose pose_to_camera (1, J, 4, 4), bound to the parts: the RiggedMesh of
         mesh_rendering.extract_rigged_mesh (vertices, triangles, joints and weights (V, max_influences), kept_mass, the
         rest part frames and bone lengths, optional colours and labels). One skin-weight launch more than extract_mesh;
         `texture_size` adds the texture atlas of the mesh, baked in this pose in `texture_color`."""
         from ..libraries.NARF.mesh_rendering import extract_rigged_mesh
         center, pose_parts, model_input = self._mesh_inputs(pose_to_camera, z, z_rend, bone_length, truncation_psi)
         return extract_rigged_mesh(self, pose_parts, center, voxel_size, mesh_th, model_input, max_influences, return_colors,
-                                   return_part_labels, texture_size, texture_color)
+                                   return_part_labels, texture_size, texture_color, simplify_cell)
 
     def bake_texture(self, pose_to_camera, z, z_rend, bone_length, vertices, triangles, truncation_psi=0.4, size=1024,
                      color="field", palette=None, color_fn=None, want_float=False):
@@ -388,8 +390,10 @@ class TriPlaneNARF(nn.Module):
         return bake_texture(self, pose_parts, vertices, triangles, model_input, size, color, palette, color_fn, want_float)
 
     def render_textured_mesh(self, pose_to_camera, intrinsics, z, z_rend, bone_length, voxel_size=0.01, mesh_th=15,
-                             truncation_psi=0.4, img_size=128, texture_size=1024, color="field", lit=True):
-        """render_colored_mesh with the colour in a texture instead of on the vertices: extract_mesh -> bake_texture ->
+                             truncation_psi=0.4, img_size=128, texture_size=1024, color="field", lit=True,
+                             simplify_cell=None):
+        """render_colored_mesh with the colour in a texture instead of on the vertices: extract_mesh (simplified to cells of
+        `simplify_cell` when that is given) -> bake_texture ->
         paint_textured_mesh (HIP rasteriser, HIP textured shading, 512 x 512), one host copy of the finished image. The
         colour resolution is the atlas's, not the mesh's: a coarse mesh keeps the field's detail. Returns (image
         (512, 512, 3) uint8 numpy, (vertices, triangles, the TextureAtlas)); one sample."""
@@ -397,7 +401,8 @@ class TriPlaneNARF(nn.Module):
         if color not in ("field", "parts"):
             raise ValueError(f"color is 'field' (the radiance field's colour) or 'parts' (the part labels), got {color!r}")
         center, pose_parts, model_input = self._mesh_inputs(pose_to_camera, z, z_rend, bone_length, truncation_psi)
-        vertices, triangles = extract_mesh(self, pose_parts, center, voxel_size, mesh_th, model_input)
+        vertices, triangles = extract_mesh(self, pose_parts, center, voxel_size, mesh_th, model_input,
+                                           simplify_cell=simplify_cell)
         atlas = bake_texture(self, pose_parts, vertices, triangles, model_input, texture_size, color)
         _, painted = paint_textured_mesh(vertices, triangles, atlas, intrinsics, img_size, lit=lit)
         return painted.image.cpu().numpy(), (vertices, triangles, atlas)
@@ -425,14 +430,15 @@ class TriPlaneNARF(nn.Module):
         image = rasterize_mesh(vertices, triangles, intrinsics, img_size).image
         return image.cpu().numpy(), (vertices, triangles)
 
-    def _colored_mesh(self, pose_to_camera, z, z_rend, bone_length, voxel_size, mesh_th, truncation_psi, color):
+    def _colored_mesh(self, pose_to_camera, z, z_rend, bone_length, voxel_size, mesh_th, truncation_psi, color,
+                      simplify_cell=None):
         """(vertices, triangles, colours or labels, the keywords paint_mesh takes for them) of render_colored_mesh"""
         from ..libraries.NeRF.rendering import semantic_palette
         if color not in ("field", "parts"):
             raise ValueError(f"color is 'field' (the radiance field's colour) or 'parts' (the part labels), got {color!r}")
         vertices, triangles, paint = self.extract_mesh(pose_to_camera, z, z_rend, bone_length, voxel_size, mesh_th,
                                                        truncation_psi, return_part_labels=color == "parts",
-                                                       return_colors=color == "field")
+                                                       return_colors=color == "field", simplify_cell=simplify_cell)
         if color == "field":
             return vertices, triangles, paint, dict(vertex_colors=paint)
         palette = (semantic_palette(self.num_bone, vertices.device) + 1) / 2

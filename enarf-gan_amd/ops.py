@@ -992,6 +992,29 @@ def shade_textured(pix_to_face: torch.Tensor, bary: torch.Tensor, normals: torch
     return _bake_lib.shade_textured(pix_to_face, bary, normals, vertices, triangles, texture, lit, background)
 
 
+# ------------------------------------------------------------------------------------------------- simplified meshes
+def simplify_mesh(vertices: torch.Tensor, triangles: torch.Tensor, cell: float, origin=None, placement: str = "quadric",
+                  reg: float = 1e-3):
+    """A mesh simplified by uniform-grid vertex clustering (libenarf_simp.so; the contract is in include/enarf_simp.h): the
+    named tuple (vertices (C, 3) fp32, triangles (T', 3) int64, vertex_cluster (V,) int32, cluster_size (C,) int32) on the
+    mesh's device. vertices (V, 3) fp32 and triangles (T, 3) int64 device tensors; `cell` the cell size h > 0, taken as
+    fp32; `origin` three fp32 at or below the vertices' minimum (the default: the minimum itself). Every vertex falls into
+    the cell floor((v - origin) / h); every non-empty cell becomes one vertex (numbered by ascending cx, cy, cz), placed at
+      placement="mean"     the mean of the cell's vertices;
+      placement="quadric"  the point nearest the planes of the fine triangles that touch the cell, each weighed by its
+                           squared area, regularised toward the mean with `reg` x trace and clamped to the cell's box;
+    triangles with two corners in a cell are dropped, the others renamed, one copy of each distinct oriented triple kept,
+    in lexicographic order with the smallest index first in each. All fp64 from the stored fp32, every sum in a fixed
+    order, no atomics: two calls give the same bits. The output sizes depend on the data, so the call synchronises with
+    the host (for the vertices' bounds, the cluster count and the compaction of the triples). ValueError /
+    NotImplementedError before any launch for wrong shapes or dtypes, a cell that is not finite and > 0, non-finite
+    vertices, an origin above the minimum, 2^21 cells or more on an axis, V or 3 T >= 2^31 and an unknown placement; an
+    empty mesh gives empty outputs and launches nothing. Clustering does not preserve topology: thin gaps can close and
+    edges can become non-manifold. There is no CPU fallback."""
+    from . import _simp_lib
+    return _simp_lib.simplify_mesh(vertices, triangles, cell, origin, placement, reg)
+
+
 # ------------------------------------------------------------------------------------------------- rigged meshes
 def skin_weights(vertices: torch.Tensor, parts_rest: torch.Tensor, canonical_pose: torch.Tensor, tri_plane: torch.Tensor, *,
                  max_influences: int = 4, clamp_mask: bool = False, uniform_part_weight: bool = False,

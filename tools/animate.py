@@ -28,7 +28,9 @@ inverse depth between `--depth-range` - from the disparity of each frame (ops.ge
 writes that rig as a skinned binary glTF (mesh_rendering.export_glb), with or without --skinned-mesh. `--texture-size N`
 bakes the field's colour into an N x N texture atlas of that mesh (libenarf_bake.so): the glTF then carries the texture in
 place of the vertex colours, and `--skinned-mesh texture` draws the posed mesh with it; `--clip` writes the interpolated
-sequence into the glTF as an animation clip."""
+sequence into the glTF as an animation clip. `--simplify CELL` simplifies the extracted mesh of --skinned-mesh,
+--mesh-turntable and --export-glb to cells of CELL (libenarf_simp.so: vertex clustering with quadric placement) before it is
+coloured, rigged and baked: extract at a fine --voxel-size, keep few triangles."""
 import argparse
 import math
 import os
@@ -72,6 +74,9 @@ def main():
     ap.add_argument("--clip", action="store_true",
                     help="--export-glb: write the interpolated sequence into the file as an animation clip")
     ap.add_argument("--fps", type=float, default=24.0, help="--clip: key frames a second")
+    ap.add_argument("--simplify", type=float, default=None, metavar="CELL",
+                    help="simplify the extracted mesh to cells of this size (the poses' units) before colouring, rigging "
+                         "and baking it")
     ap.add_argument("--voxel-size", type=float, default=0.003, help="mesh turntable: the density sweep's voxel")
     ap.add_argument("--mesh-th", type=float, default=15.0, help="mesh turntable: the density threshold")
     ap.add_argument("--unlit", action="store_true", help="mesh turntable: the colour itself, without the Phong terms")
@@ -111,7 +116,8 @@ def main():
         rig = gen.extract_rigged_mesh(key_poses[:1].float(), z, bone_length, voxel_size=args.voxel_size, mesh_th=args.mesh_th,
                                       truncation_psi=args.truncation_psi, max_influences=args.influences,
                                       return_colors=True, return_part_labels=True,
-                                      texture_size=1024 if textured and args.texture_size is None else args.texture_size)
+                                      texture_size=1024 if textured and args.texture_size is None else args.texture_size,
+                                      simplify_cell=args.simplify)
         if args.export_glb:
             from enarf_gan_amd import ops
             from enarf_gan_amd.libraries.NARF.mesh_rendering import export_glb
@@ -139,7 +145,7 @@ def main():
         frames = gen.render_mesh_turntable(key_poses[:1].float(), intrinsics, z, bone_length, angles,
                                            voxel_size=args.voxel_size, mesh_th=args.mesh_th,
                                            truncation_psi=args.truncation_psi, color=args.mesh_turntable,
-                                           lit=not args.unlit, render_size=args.render_size)
+                                           lit=not args.unlit, render_size=args.render_size, simplify_cell=args.simplify)
     elif args.geometry:
         near, far = (float(v) for v in args.depth_range.split(","))
         frames, _, _ = gen.render_geometry_animation(key_poses, bone_length, intrinsics, z, num=args.num,

@@ -214,7 +214,8 @@ struct RayQueue {
     }
     // ONE thread (any - the cursor lives in LDS): take the next ray off the queues and leave its id and its set-up
     // record in slot; id -1 once every list is drained. The whole dependent chain (atomic -> list entry -> record) runs
-    // here, on a wave that has nothing else to do, so the other waves find the record in LDS.
+    // here, on a wave that has nothing else to do (render_kernel: the first to finish its coarse tile), so the other
+    // waves find the record in LDS.
     __device__ __forceinline__ void pop(int slot) {
         int lid = -1, idx = 0;
         int *cur = l_q + kQCursorOff;
@@ -276,7 +277,8 @@ static_assert(kSlotWords % 4 == 0 && SL_REC % 4 == 0 && SL_NEXT_REC % 4 == 0, "s
 static_assert(kQSlotInts % 2 == 0, "RayQueue::get_with_flag loads 8 aligned bytes");
 
 // scratch section of the dynamic LDS (floats): render_kernel's [ray record][Nc + 1 bin edges][4 waves x 32 candidate ids]
-// [RayQueue ints][fine_done: render_kernel's count of finished fine passes, one per wave and ray]
+// [RayQueue ints][fine_done: render_kernel's count of finished fine passes, one per wave and ray; the word after it: its
+// count of finished coarse passes, which hands the pop and S2 to the first two waves]
 constexpr int SC_SLOT = 0;
 constexpr int SC_BTAB = SC_SLOT + kSlotWords;
 constexpr int SC_CAND = SC_BTAB + (kMaxSamples + 1 + 3) / 4 * 4;

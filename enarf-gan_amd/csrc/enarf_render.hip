@@ -731,7 +731,10 @@ __global__ __launch_bounds__(256, kRenderWavesPerSimd) void render_kernel(const 
     // fine passes finished in this workgroup: every wave adds 1 per ray, so 4 x (rays done) once a ray's fine tiles are
     // complete; only ever counts up (a launch has fewer than 2^31 rays)
     unsigned *l_fine_done = reinterpret_cast<unsigned *>(scratch + SC_FINE_DONE);
-    if (tid == 0) { *l_fine_done = 0u; rq.set_flag(0); }
+    // waves that have finished their coarse tiles of the ray (the word after it): likewise 1 per wave and ray, so a wave
+    // that reads 4 x (rays done) + k there is the k-th to get to the S1 barrier (the difference is taken modulo 2^32)
+    unsigned *l_coarse_done = l_fine_done + 1;
+    if (tid == 0) { *l_fine_done = 0u; *l_coarse_done = 0u; rq.set_flag(0); }
     __syncthreads();                          // the staged image context is complete before any wave starts a tile
 
     MarchCounters C{0u, 0u, 0u, 0u, 0u};
@@ -740,10 +743,6 @@ __global__ __launch_bounds__(256, kRenderWavesPerSimd) void render_kernel(const 
 
     while (cur >= 0) {
         const uint32_t rid = (uint32_t)cur;
-        // next entry (read after the S1 barrier): popped by the wave that has no coarse tile in this ray, when there is
-        // one - the atomic's round trip then costs nothing
-        const int spare_wave = (3 * SPL * 16 >= Nc) ? ((3 - (int)(rid & 3u)) & 3) : 0;
-        if (wave == spare_wave && lane == 0) rq.pop(qslot ^ 1);
         const int nb = (int)(rid / (uint32_t)n);
         if (nb != b) {   // next image: restage its MLP pack and part frames (the lists are in image order, so this is rare)
             b = nb;
@@ -773,12 +772,24 @@ __global__ __launch_bounds__(256, kRenderWavesPerSimd) void render_kernel(const 
                 ray_tile<MODE>(a, S, l_btab, l_cand, ncand, sw, seg, false, t, lane, C);
             }
         }
-        // the sorted uniforms of the importance draw do not depend on the coarse pass: the wave that will run S2 draws
-        // them now, while the others are still in their coarse tiles
+        // ---- the two jobs one wave does for the workgroup ahead of the S1 barrier go to the waves that get here FIRST,
+        // whichever they are: the first pops the next entry (read after the barrier) - a queue head's atomic, the list entry
+        // and the ray record, three dependent round trips, 2.4 us in the median and 5 us under contention - and the second
+        // draws the sorted uniforms of the importance draw, which do not depend on the coarse pass, and runs S2 with them.
+        // Both used to be the job of the wave without a coarse tile in this ray (wave 0 where there is none). That wave
+        // composited the previous ray first, so behind short coarse tiles (rays with few candidate parts) it came to the
+        // barrier last, with the pop still ahead of it; behind long ones it still is the first here and pops as before.
+        // Which wave does what changes no result: the pop's order among workgroups is arbitrary anyway, and the draw is a
+        // function of the ray id and the seed.
+        unsigned turn = 0u;
+        if (lane == 0) turn = __hip_atomic_fetch_add(l_coarse_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) - fine_target;
+        turn = (unsigned)__builtin_amdgcn_readfirstlane((int)turn);    // 0 .. 3, each exactly once per ray
+        if (turn == 0u && lane == 0) rq.pop(qslot ^ 1);
+        const bool s2_wave = turn == 1u;
         float usort[SPL];
 #pragma unroll
         for (int s = 0; s < SPL; ++s) usort[s] = 0.0f;
-        if (wave == spare_wave && !a.bins) draw_sorted_uniforms<SPL>(a, rid, Nf, lane, usort);
+        if (s2_wave && !a.bins) draw_sorted_uniforms<SPL>(a, rid, Nf, lane, usort);
         __syncthreads();
         const int2 popped = rq.get_with_flag(qslot ^ 1);
         const int next_ray = popped.x;
@@ -789,7 +800,7 @@ __global__ __launch_bounds__(256, kRenderWavesPerSimd) void render_kernel(const 
 
         // ---- S2 on ONE wave: the result goes through LDS; the other waves wait at the barrier instead of spending the
         // same ~350 VALU instructions each (the SIMDs are shared with two other workgroups that can use the slots).
-        if (wave == spare_wave) {
+        if (s2_wave) {
             __builtin_amdgcn_s_setprio(kS2Prio);
             ray_sample_stage<SPL>(a, l_btab, sw, rid, rec.dmin, rec.dmax, usort, S.mult_w, lane);
             __builtin_amdgcn_s_setprio(0);
@@ -818,7 +829,8 @@ __global__ __launch_bounds__(256, kRenderWavesPerSimd) void render_kernel(const 
 
         // ---- S4 on one wave, while the other waves are already in the next ray's coarse pass - on the wave that has no
         // coarse tile there, when there is one (otherwise wave 0, before its coarse tile; also the last ray's S4, whose
-        // three other waves have counted themselves in before they left the kernel).
+        // three other waves have counted themselves in before they left the kernel). S4 is all that wave has to do ahead
+        // of the next S1 barrier unless it still is among the first two there (above).
         const int s4_wave = (next_ray >= 0 && 3 * SPL * 16 >= Nc) ? ((3 - (next_ray & 3)) & 3) : 0;
         if (wave == s4_wave) {
             unsigned polls = 0u;
@@ -848,7 +860,10 @@ __global__ __launch_bounds__(256, kRenderWavesPerSimd) void render_kernel(const 
         //  * coarse arrays: rewritten by the next coarse tiles, which may now start while other waves are still in this
         //    ray's fine tiles; their last reader was this ray's S2, complete before the S2 barrier every wave has passed;
         //  * the ray's record and id: register copies since the top of the loop, so the pop that recycles the queue slot
-        //    (by the next ray's spare wave, which has passed this ray's S2 barrier) takes nothing away;
+        //    (by whichever wave finishes its coarse tile of the next ray first: it has passed this ray's S2 barrier, and the
+        //    slot's last readers were all ahead of this ray's S1 barrier) takes nothing away, also while S4 is still running;
+        //    the queue's cursor is touched by the popping lane alone, and two pops are an S1 barrier apart;
+        //  * the turn count: every wave adds 1 per ray between two S1 barriers, so it stands at 4 x (rays done) behind each;
         //  * change of image: the restage path above keeps its full barrier - a slow wave may still be in a fine tile on the
         //    old image's pack - and the S4 wave joins it after S4;
         //  * last ray (next_ray < 0): three waves leave the loop, wave 0 waits for all four counts and composites.

@@ -45,6 +45,7 @@ SIDE_LIBRARIES = {
     "pgrad": (["enarf_pgrad.hip"], "enarf_pgrad.h"),       # the query's gradient for the sample points and the part frames
     "scene": (["enarf_scene.hip"], "enarf_scene.h"),       # several avatars marched on the same rays, composed into one image
     "sgrad": (["enarf_sgrad.hip"], "enarf_sgrad.h"),       # the scene composite's gradient for the avatars' densities and colours
+    "nrm": (["enarf_nrm.hip"], "enarf_nrm.h"),             # the density's spatial gradient: ray, pixel and vertex normals
     "skin": (["enarf_skin.hip"], "enarf_skin.h"),          # skin weights of mesh vertices, linear-blend posing of the mesh
 }
 ALL_LIBRARIES = {**LIBRARIES, **SIDE_LIBRARIES}

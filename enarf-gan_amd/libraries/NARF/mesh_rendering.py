@@ -21,6 +21,8 @@ weights and the texture are computed on the small mesh.
 from __future__ import annotations
 
 import dataclasses
+import functools
+import inspect
 from typing import Dict, Optional
 
 import torch
@@ -148,6 +150,80 @@ def vertex_colors(model, pose_to_camera: torch.Tensor, vertices: torch.Tensor, m
 
 
 @torch.no_grad()
+def field_normals(model, pose_to_camera: torch.Tensor, points: torch.Tensor, model_input: Dict = {},
+                  fallback: Optional[torch.Tensor] = None, min_gradient: float = 0.0) -> torch.Tensor:
+    """(N, 3) fp32 unit normals of the field at points (N, 3) in camera coordinates: -grad(density) / |grad(density)|, the
+    density growing into the body. Where |grad| <= min_gradient (the scaled space's units; outside every cube and where
+    the density head is off the gradient is an exact zero) the point takes `fallback` (N, 3) as given, or zeros. One
+    ops.field_gradient launch over the point array; pose_to_camera (1, P, 4, 4) part frames with UNSCALED translation, as
+    for vertex_colors. The scale between camera and scaled space is uniform, so the direction is that of either."""
+    from ..NeRF.rendering import _parts_from_part_poses
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"field_normals takes (N, 3) points, got {tuple(points.shape)}")
+    if fallback is not None and tuple(fallback.shape) != tuple(points.shape):
+        raise ValueError(f"field_normals takes a fallback of the points' shape {tuple(points.shape)}, got {tuple(fallback.shape)}")
+    parts = _parts_from_part_poses(model, pose_to_camera, model_input["bone_length"])
+    tri, feat_cl = model._tri_plane_pair(model_input)
+    pack = model._mlp_pack(model_input["z_rend"])
+    cs = model.coordinate_scale
+    scaled = (points.float() * cs if cs != 1 else points.float()).t()[None].contiguous()
+    _, gradient = ops.field_gradient(scaled, parts, model.canonical_pose, tri, feat_cl, pack, **model.kernel_flags())
+    g = gradient[0].t()
+    m = torch.linalg.vector_norm(g, dim=1, keepdim=True)
+    has = (m > min_gradient) & torch.isfinite(m)
+    other = torch.zeros_like(g) if fallback is None else fallback.to(g.dtype)
+    return torch.where(has, -g / torch.where(has, m, torch.ones_like(m)), other).contiguous()
+
+
+def pixel_field_normals(fragments, vertices: torch.Tensor, triangles: torch.Tensor, field) -> torch.Tensor:
+    """The (R, R, 3) normal buffer of paint_mesh(normals="field"): the surface point of every covered pixel, formed from
+    the fragment's face, its barycentrics and the vertices, takes the field's normal there (field_normals, one launch
+    over the R^2 points) with the rasteriser's interpolated normal as the fallback; an uncovered pixel keeps the
+    rasteriser's. `field` = (model, pose_to_camera, model_input) as field_normals takes them."""
+    model, pose_to_camera, model_input = field
+    face = fragments.pix_to_face
+    covered = face >= 0
+    corners = vertices.float()[triangles[face.clamp(min=0)]]                      # (R, R, 3 corners, 3)
+    points = (fragments.bary[..., None] * corners).sum(dim=-2)
+    normals = field_normals(model, pose_to_camera, points.reshape(-1, 3), model_input,
+                            fallback=fragments.normals.reshape(-1, 3)).reshape(fragments.normals.shape)
+    return torch.where(covered[..., None], normals, fragments.normals).contiguous()
+
+
+def _shading_normals(fragments, vertices, triangles, normals, field):
+    if normals == "mesh":
+        return fragments.normals
+    if normals != "field":
+        raise ValueError(f"normals is 'mesh' (the rasteriser's interpolated face normals) or 'field' (the density gradient at "
+                         f"every covered pixel), got {normals!r}")
+    if field is None:
+        raise ValueError("normals='field' takes field=(model, pose_to_camera, model_input), the field the mesh came from")
+    return pixel_field_normals(fragments, vertices, triangles, field)
+
+
+def _adds_return_normals(field_of):
+    """Decorator of a mesh extractor whose result starts with (vertices, triangles): adds the keyword `return_normals`,
+    which appends (V, 3) fp32 unit normals - the field's own normal at each final vertex (field_normals, one gradient
+    launch; zeros where the field has no gradient). field_of(arguments) -> (model, part frames, model_input), from the
+    extractor's bound arguments. The extractor keeps its signature: the keyword belongs to the wrapper."""
+    def decorate(extract):
+        signature = inspect.signature(extract)
+
+        @functools.wraps(extract)
+        def wrapper(*args, return_normals: bool = False, **kwargs):
+            out = extract(*args, **kwargs)
+            if not return_normals:
+                return out
+            bound = signature.bind(*args, **kwargs)
+            bound.apply_defaults()
+            model, pose_parts, model_input = field_of(bound.arguments)
+            return tuple(out) + (field_normals(model, pose_parts, out[0], model_input),)
+        return wrapper
+    return decorate
+
+
+@_adds_return_normals(lambda a: (a["model"], a["pose_to_camera"], a["model_input"]))
+@torch.no_grad()
 def extract_mesh(model, pose_to_camera: torch.Tensor, center: torch.Tensor, voxel_size: float = 0.003, mesh_th: float = 15,
                  model_input: Dict = {}, return_part_labels: bool = False, return_colors: bool = False,
                  simplify_cell: Optional[float] = None):
@@ -157,7 +233,9 @@ def extract_mesh(model, pose_to_camera: torch.Tensor, center: torch.Tensor, voxe
     point_part_labels launch over the vertex array; `return_colors` adds (V, 3) fp32 in [0, 1], the field's colour at
     each vertex (vertex_colors, one query launch); with both the result is (vertices, triangles, labels, colors).
     `simplify_cell` = h simplifies the mesh straight after the transform (ops.simplify_mesh(vertices, triangles, h):
-    extract fine, cluster to cells of h camera units); labels and colours are then those of the simplified vertices."""
+    extract fine, cluster to cells of h camera units); labels and colours are then those of the simplified vertices.
+    The keyword `return_normals` (of the decorator above) adds, last, (V, 3) fp32 unit normals: the field's own normal at
+    each final vertex, after the simplification - the shading normal does not degrade with the triangle count."""
     if pose_to_camera.device.type != "cuda":
         raise _mesh_lib.EnarfHipError("extract_mesh runs on the device (there is no CPU fallback)")
     density = density_volume(model, pose_to_camera, center, voxel_size, model_input)
@@ -385,14 +463,18 @@ def _host(a, dtype=None):
     return a if dtype is None else a.astype(dtype)
 
 
-def export_obj(vertices, triangles, path: str, colors=None) -> None:
+def export_obj(vertices, triangles, path: str, colors=None, normals=None) -> None:
     """Plain-text Wavefront OBJ ("v x y z" lines, then "f a b c" with 1-based indices), as mcubes.export_obj writes.
-    With `colors` (V, 3) in [0, 1] the vertex lines are "v x y z r g b", the extension MeshLab and Blender read."""
+    With `colors` (V, 3) in [0, 1] the vertex lines are "v x y z r g b", the extension MeshLab and Blender read. With
+    `normals` (V, 3) a "vn x y z" line per vertex follows the vertices and the faces read "f a//a b//b c//c"."""
     import numpy as np
     v, f = _host(vertices), _host(triangles)
     c = None if colors is None else _host(colors)
     if c is not None and c.shape != (len(v), 3):
         raise ValueError(f"export_obj takes ({len(v)}, 3) colors, got {c.shape}")
+    vn = None if normals is None else _host(normals)
+    if vn is not None and vn.shape != (len(v), 3):
+        raise ValueError(f"export_obj takes ({len(v)}, 3) normals, got {vn.shape}")
     with open(path, "w") as fh:
         for i, x in enumerate(v):
             if c is None:
@@ -400,12 +482,19 @@ def export_obj(vertices, triangles, path: str, colors=None) -> None:
             else:
                 fh.write("v %r %r %r %r %r %r\n" % (float(x[0]), float(x[1]), float(x[2]),
                                                    float(c[i, 0]), float(c[i, 1]), float(c[i, 2])))
+        if vn is not None:
+            for x in vn:
+                fh.write("vn %r %r %r\n" % (float(x[0]), float(x[1]), float(x[2])))
         for t in f.astype(np.int64) + 1:
-            fh.write("f %d %d %d\n" % (t[0], t[1], t[2]))
+            if vn is None:
+                fh.write("f %d %d %d\n" % (t[0], t[1], t[2]))
+            else:
+                fh.write("f %d//%d %d//%d %d//%d\n" % (t[0], t[0], t[1], t[1], t[2], t[2]))
 
 
-def export_ply(vertices, triangles, path: str, colors=None, labels=None) -> None:
-    """Binary little-endian PLY: per vertex float x y z, with `colors` (V, 3) in [0, 1] uchar red green blue =
+def export_ply(vertices, triangles, path: str, colors=None, labels=None, normals=None) -> None:
+    """Binary little-endian PLY: per vertex float x y z, with `normals` (V, 3) float nx ny nz (straight after the
+    position, where readers expect them), with `colors` (V, 3) in [0, 1] uchar red green blue =
     floor(255 clamp(c, 0, 1)) (the bytes the painted image uses), with `labels` (V,) int `part`; per face
     `list uchar int vertex_indices` (0-based)."""
     import numpy as np
@@ -413,6 +502,12 @@ def export_ply(vertices, triangles, path: str, colors=None, labels=None) -> None
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
     header = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}",
               "property float x", "property float y", "property float z"]
+    if normals is not None:
+        vn = _host(normals, np.float32)
+        if vn.shape != (len(v), 3):
+            raise ValueError(f"export_ply takes ({len(v)}, 3) normals, got {vn.shape}")
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        header += ["property float nx", "property float ny", "property float nz"]
     if colors is not None:
         c = _host(colors, np.float64)
         if c.shape != (len(v), 3):
@@ -430,6 +525,8 @@ def export_ply(vertices, triangles, path: str, colors=None, labels=None) -> None
     header += [f"element face {len(f)}", "property list uchar int vertex_indices", "end_header"]
     vert = np.zeros(len(v), dtype=fields)
     vert["x"], vert["y"], vert["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if normals is not None:
+        vert["nx"], vert["ny"], vert["nz"] = vn[:, 0], vn[:, 1], vn[:, 2]
     if colors is not None:
         with np.errstate(invalid="ignore"):
             byte = np.floor(255 * np.clip(np.nan_to_num(c, nan=0.0), 0, 1)).astype(np.uint8)
@@ -480,7 +577,8 @@ def _png_rgba(pixels) -> bytes:
             + chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + chunk(b"IEND", b""))
 
 
-def export_glb(rig: RiggedMesh, path: str, texture: Optional[TextureAtlas] = None, clips: Optional[Dict] = None) -> None:
+def export_glb(rig: RiggedMesh, path: str, texture: Optional[TextureAtlas] = None, clips: Optional[Dict] = None,
+               normals=None) -> None:
     """The rigged mesh as binary glTF 2.0 (standard library and numpy only): one mesh primitive with POSITION, optional
     COLOR_0 (float RGB), JOINTS_0 / WEIGHTS_0 and, at 8 influences, JOINTS_1 / WEIGHTS_1 (joints as unsigned bytes, an
     unused slot as joint 0 with weight 0), 32-bit indices; a flat skeleton of P joint nodes under one identity root, node
@@ -498,7 +596,11 @@ def export_glb(rig: RiggedMesh, path: str, texture: Optional[TextureAtlas] = Non
     rotation and a scale sampler for every part node, interpolation LINEAR: the rotation keys are unit quaternions whose
     sign follows the previous key (no key has a negative dot product with its predecessor), the scale is bone_length /
     rest bone_length, uniform. A viewer that plays a clip shows skin_mesh of its poses at the keys. With neither a texture
-    nor clips the file is the one earlier versions wrote, byte for byte."""
+    nor clips the file is the one earlier versions wrote, byte for byte.
+
+    `normals` (V, 3): the NORMAL attribute (float VEC3) of the rest pose, e.g. extract_mesh(return_normals=True)'s or
+    field_normals at rig.vertices - de-indexed with the primitive when a texture is written; viewers skin it themselves.
+    normals=None writes the bytes a call without the keyword writes."""
     import json
     import struct
     import numpy as np
@@ -514,6 +616,9 @@ def export_glb(rig: RiggedMesh, path: str, texture: Optional[TextureAtlas] = Non
         raise ValueError(f"export_glb: joints up to {int(joints.max())} with {P} parts (joints are unsigned bytes)")
     if len(f) and (f.min() < 0 or f.max() >= len(v)):
         raise ValueError("export_glb: a triangle names a vertex the mesh does not have")
+    vn = None if normals is None else _host(normals, np.float32)
+    if vn is not None and vn.shape != (len(v), 3):
+        raise ValueError(f"export_glb takes ({len(v)}, 3) normals, got {vn.shape}")
     weights = np.where(joints >= 0, weights, np.float32(0)).astype(np.float32)
     joints = np.where(joints >= 0, joints, 0).astype(np.uint8)
     R, t = frames[:, :3, :3], frames[:, :3, 3]
@@ -546,8 +651,11 @@ def export_glb(rig: RiggedMesh, path: str, texture: Optional[TextureAtlas] = Non
             raise ValueError(f"export_glb takes a ({texture.size}, {texture.size}, 4) uint8 texture, got {pixels.shape}")
         corner = f.reshape(-1)                             # every corner a vertex of its own: its triangle's UV
         v, joints, weights = v[corner], joints[corner], weights[corner]
+        vn = None if vn is None else vn[corner]
         f = np.arange(len(corner), dtype=np.int64).reshape(-1, 3)
     attributes = {"POSITION": add(v, "VEC3", FLOAT, ARRAY, bounds=len(v) > 0)}
+    if vn is not None:
+        attributes["NORMAL"] = add(vn, "VEC3", FLOAT, ARRAY)
     if texture is not None:
         attributes["TEXCOORD_0"] = add(atlas_uv(texture.num_triangles, texture.size).reshape(-1, 2), "VEC2", FLOAT, ARRAY)
     elif rig.colors is not None:
@@ -672,32 +780,37 @@ def rasterize_mesh(vertices: torch.Tensor, triangles: torch.Tensor, intrinsics, 
 
 
 def paint_mesh(vertices: torch.Tensor, triangles: torch.Tensor, intrinsics, img_size: int, render_size: int = 512,
-               vertex_colors=None, vertex_labels=None, palette=None, lit: bool = True):
+               vertex_colors=None, vertex_labels=None, palette=None, lit: bool = True, normals: str = "mesh", field=None):
     """The mesh drawn in its vertex colours (V, 3) fp32 in [0, 1], or in the palette (P, 3) colours of its vertex labels
     (V,) int32: rasterize_mesh, then ops.shade_fragments on its fragment buffers (libenarf_paint.so, one launch more),
     with no host synchronisation. Returns (the RasterizedMesh of rasterize_mesh, the namedtuple (image (R, R, 3) uint8,
     albedo, shaded (R, R, 3) fp32) of shade_fragments). With `lit` the colours take the rasteriser's hard-Phong terms
-    (white colours then give rasterize_mesh's own image); without, the image is the colour itself. No CPU fallback."""
+    (white colours then give rasterize_mesh's own image); without, the image is the colour itself. normals="field" with
+    field=(model, pose_to_camera, model_input) shades every covered pixel with the field's own normal at its surface point
+    (pixel_field_normals: R^2 points, one gradient launch) instead of the interpolated face normal: per-pixel normal
+    mapping without an atlas. No CPU fallback."""
     fragments = rasterize_mesh(vertices, triangles, intrinsics, img_size, render_size)
-    painted = ops.shade_fragments(fragments.pix_to_face, fragments.bary, fragments.normals, vertices, triangles,
+    painted = ops.shade_fragments(fragments.pix_to_face, fragments.bary,
+                                  _shading_normals(fragments, vertices, triangles, normals, field), vertices, triangles,
                                   vertex_colors=vertex_colors, vertex_labels=vertex_labels, palette=palette, lit=lit)
     return fragments, painted
 
 
 def paint_textured_mesh(vertices: torch.Tensor, triangles: torch.Tensor, atlas: TextureAtlas, intrinsics, img_size: int,
-                        render_size: int = 512, lit: bool = True, use_float: bool = False):
+                        render_size: int = 512, lit: bool = True, use_float: bool = False, normals: str = "mesh", field=None):
     """The mesh drawn with its texture atlas: rasterize_mesh, then ops.shade_textured on its fragment buffers
     (libenarf_bake.so, one launch more), with no host synchronisation. Returns what paint_mesh returns: (the
     RasterizedMesh, the namedtuple (image (R, R, 3) uint8, albedo, shaded (R, R, 3) fp32)). The albedo is one bilinear tap
     of atlas.texture (of atlas.texture_f32 with `use_float`); the mesh may be posed (skin_mesh), the triangles are the
-    atlas's. No CPU fallback."""
+    atlas's. `normals` and `field` as in paint_mesh. No CPU fallback."""
     if atlas.num_triangles != triangles.shape[0]:
         raise ValueError(f"paint_textured_mesh: the atlas was baked for {atlas.num_triangles} triangles, the mesh has "
                          f"{triangles.shape[0]}")
     if use_float and atlas.texture_f32 is None:
         raise ValueError("paint_textured_mesh: use_float takes an atlas baked with want_float=True")
     fragments = rasterize_mesh(vertices, triangles, intrinsics, img_size, render_size)
-    painted = ops.shade_textured(fragments.pix_to_face, fragments.bary, fragments.normals, vertices, triangles,
+    painted = ops.shade_textured(fragments.pix_to_face, fragments.bary,
+                                 _shading_normals(fragments, vertices, triangles, normals, field), vertices, triangles,
                                  atlas.texture_f32 if use_float else atlas.texture, lit=lit)
     return fragments, painted
 

@@ -263,10 +263,12 @@ def composite_fine(density: torch.Tensor, color: torch.Tensor, depth: torch.Tens
     return (w[:, None] * color[..., :-1]).sum(dim=-1), w.sum(dim=-1), (w * 1 / depth[..., :-1]).sum(dim=-1), w
 
 
-def _fixed_samples(model, image_coord, inv_intrinsics, parts, tri, feat_cl, pack, Nc, Nf, render_scale, bins, seed):
+def _fixed_samples(model, image_coord, inv_intrinsics, parts, tri, feat_cl, pack, Nc, Nf, render_scale, bins, seed,
+                   with_outputs=False):
     """The sample positions a posable render holds fixed, from one march with its taps (call under no_grad): image_coord
     (B, 1, 3, n) or (B, 3, n), inv_intrinsics (3, 3) or (B, 3, 3) -> (the march's taps, fine_points (B, 3, n Nf) formed from
-    bins, depth_min and depth_max as return_intermediate forms them, fine_depth (B, n, Nf))."""
+    bins, depth_min and depth_max as return_intermediate forms them, fine_depth (B, n, Nf)); `with_outputs` adds the
+    march's own RenderOutputs (colour, mask, disparity, fine_weights)."""
     B, n = image_coord.shape[0], image_coord.shape[-1]
     out = ops.render_fwd(image_coord, inv_intrinsics, parts, model.canonical_pose, tri, feat_cl, pack, Nc, Nf,
                          render_scale=render_scale, bins=bins, seed=seed, mlp_mode=model.mlp_mode, debug=True,
@@ -281,7 +283,57 @@ def _fixed_samples(model, image_coord, inv_intrinsics, parts, tri, feat_cl, pack
     start, end = (t["depth_min"][:, None] * ray)[..., None], (t["depth_max"][:, None] * ray)[..., None]
     fine_points = (start * (1 - b_) + end * b_).reshape(B, 3, n * Nf)
     fine_depth = t["depth_min"][..., None] * (1 - t["bins"]) + t["depth_max"][..., None] * t["bins"]
+    if with_outputs:
+        return t, fine_points, fine_depth, out
     return t, fine_points, fine_depth
+
+
+def _march_with_gradient(model, image_coord, inv_intrinsics, parts, pack, Nc, Nf, render_scale, model_input, bins, seed):
+    """One march with its taps (_fixed_samples) and one ops.field_gradient launch on its fine points, under no_grad:
+    (the march's RenderOutputs, gradient (B, 3, n Nf)). The seed is drawn as render() draws it."""
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    if not hasattr(model, "buffers_tensors"):
+        model.buffers_tensors = {}
+    with torch.no_grad():
+        tri, feat_cl = model._tri_plane_pair(model_input)
+        t, fine_points, _, out = _fixed_samples(model, image_coord, inv_intrinsics, parts, tri, feat_cl, pack, Nc, Nf,
+                                                render_scale, bins, seed, with_outputs=True)
+        density, gradient = ops.field_gradient(fine_points, parts, model.canonical_pose, tri, feat_cl, pack,
+                                               **model.kernel_flags())
+    model.buffers_tensors.update(bins=t["bins"], fine_weights=out.fine_weights, fine_depth=out.fine_depth,
+                                 fine_points=fine_points, fine_gradient=gradient, fine_density=density[:, None])
+    return out, gradient
+
+
+def render_field_normals(model, image_coord: torch.Tensor, pose_to_camera: torch.Tensor, inv_intrinsics: torch.Tensor,
+                         render_scale: float = 1, Nc: int = 64, Nf: int = 128, model_input: Dict = {},
+                         bins: Optional[torch.Tensor] = None, seed: Optional[int] = None,
+                         _parts: Optional[torch.Tensor] = None, _pack: Optional[torch.Tensor] = None, **normal_kwargs):
+    """render() with the field's own normal of every ray: image_coord (B, 1, 3, n); pose_to_camera (B, P, 4, 4) part
+    frames -> (colour (B, 3, n), mask (B, n), disparity (B, n), the RayNormals of ops.ray_normals). One march with its taps
+    (as render_posable's), one ops.field_gradient launch on its fine points, one ops.ray_normals launch: the normal is
+    minus the density gradient composited with the march's own fine weights, in camera space. Colour, mask and disparity
+    are render()'s on the same seed and bins. normal_kwargs go to ops.ray_normals (fallback, flags, points, shade,
+    mask_threshold, min_gradient, background, want_magnitude). The fine points, their gradient and density are left in
+    model.buffers_tensors (fine_points, fine_gradient, fine_density). Runs under no_grad; inputs that require a gradient
+    raise NotImplementedError."""
+    assert pose_to_camera.shape[1] == model.num_bone
+    z_rend = model_input["z_rend"]
+    if torch.is_grad_enabled() and (pose_to_camera.requires_grad or z_rend.requires_grad or
+                                    model._tri_plane_graph(model_input).requires_grad or
+                                    any(p.requires_grad for p in model.mlp.as_dict().values())):
+        raise NotImplementedError("render_field_normals is not differentiable (no gradient flows through normals); call "
+                                  "it under torch.no_grad()")
+    with torch.no_grad():
+        if _parts is None:
+            _parts = _parts_from_part_poses(model, pose_to_camera, model_input["bone_length"])
+        if _pack is None:
+            _pack = model._mlp_pack(z_rend)
+        out, gradient = _march_with_gradient(model, image_coord, inv_intrinsics, _parts, _pack, Nc, Nf, render_scale,
+                                             model_input, bins, seed)
+        normals = ops.ray_normals(gradient, out.fine_weights, out.mask, **normal_kwargs)
+    return out.color, out.mask, out.disparity, normals
 
 
 def render_posable(model, image_coord: torch.Tensor, pose_to_camera: torch.Tensor, inv_intrinsics: torch.Tensor,

@@ -8,6 +8,8 @@ The background network is the StyleGAN2 skip generator of `libraries/custom_styl
 n_mlp 4, `crop_background` from the config, or the pretrained church generator), built on this repo's HIP ops; with
 `black_background=True` / `black_bg_if_possible=True` nothing of it runs.
 """
+import functools
+import inspect
 from typing import Optional
 
 import numpy as np
@@ -16,6 +18,7 @@ from torch import nn
 
 from ..libraries.custom_stylegan2.net import Generator as StyleGANGenerator
 from ..libraries.custom_stylegan2.net import PretrainedStyleGAN
+from ..libraries.NARF.mesh_rendering import _adds_return_normals
 from ..libraries.NeRF.ray_sampler import mask_based_sampler, whole_image_grid_ray_sampler
 from .narf import TriPlaneNARF
 
@@ -129,13 +132,17 @@ class TriNARFGenerator(_RendererShell):
         z_nerf, z_render, _ = self._latent_parts(z)
         return self.nerf.density_volume(pose_to_camera, z_nerf, z_render, bone_length, voxel_size, truncation_psi)
 
+    @_adds_return_normals(lambda a: a["self"].nerf.mesh_field(a["pose_to_camera"], *a["self"]._latent_parts(a["z"])[:2],
+                                                              a["bone_length"], a["truncation_psi"]))
     def extract_mesh(self, pose_to_camera, z, bone_length, voxel_size=0.003, mesh_th=15, truncation_psi=0.4,
                      return_part_labels=False, return_colors=False, simplify_cell=None):
         """create_mesh's (vertices, triangles) built on the device (HIP marching cubes); one sample, as create_mesh.
         `return_part_labels` adds the (V,) int32 part that owns each vertex, `return_colors` the (V, 3) fp32 colour of
         the field at each vertex, in [0, 1] (after the labels when both are asked for). `simplify_cell` = h simplifies
         the mesh to cells of h camera units straight after marching cubes (HIP vertex clustering with quadric placement):
-        extract fine, keep few triangles; labels and colours are then those of the simplified vertices."""
+        extract fine, keep few triangles; labels and colours are then those of the simplified vertices. The keyword
+        `return_normals` (mesh_rendering._adds_return_normals) adds, last, the (V, 3) fp32 unit normals of the field itself
+        at the final vertices (HIP density gradient)."""
         z_nerf, z_render, _ = self._latent_parts(z)
         return self.nerf.extract_mesh(pose_to_camera, z_nerf, z_render, bone_length, voxel_size, mesh_th, truncation_psi,
                                       return_part_labels, return_colors, simplify_cell)
@@ -154,16 +161,19 @@ class TriNARFGenerator(_RendererShell):
         part_map = self.nerf.buffers_tensors["part_map"]
         return color.reshape(B, 3, S, S), part_map.reshape(B, S, S), mask.reshape(B, S, S)
 
-    def render_geometry(self, pose_to_camera, bone_length, z, inv_intrinsics, truncation_psi=1, shade="normal", **buffer_kwargs):
+    def render_geometry(self, pose_to_camera, bone_length, z, inv_intrinsics, truncation_psi=1, shade="normal",
+                        normals="stencil", **buffer_kwargs):
         """The geometry of the frames forward() renders, from the march's own disparity: (image (B, S, S, 3) uint8 - the
         shape image in `shade` = "normal", "lit" or "depth" -, the GeometryBuffers of ops.geometry_buffers (depth, points,
         normals, flags, image), colour (B, 3, S, S), mask (B, S, S)), all on the device, one march and one launch more,
         with no host synchronisation inside. Depth and points are metric, in the space of pose_to_camera and of
         extract_mesh's vertices; buffer_kwargs go to ops.geometry_buffers (edge, mask_threshold, near, far, background,
-        want, ...)."""
+        want, ...). normals="field" replaces normals, flags and image by the field's own normals (the HIP density gradient
+        composited along each ray, the stencil normals as the fallback; TriPlaneNARF.render_geometry)."""
         z_nerf, z_render, _ = self._latent_parts(z)
         return self.nerf.render_geometry(pose_to_camera, inv_intrinsics, z_nerf, z_render, bone_length, self.size,
-                                         truncation_psi=truncation_psi, shade=shade, **self._samples, **buffer_kwargs)
+                                         truncation_psi=truncation_psi, shade=shade, normals=normals, **self._samples,
+                                         **buffer_kwargs)
 
     def render_extracted_mesh(self, pose_to_camera, intrinsics, z, bone_length, voxel_size=0.003, mesh_th=15,
                               truncation_psi=0.4):
@@ -174,23 +184,27 @@ class TriNARFGenerator(_RendererShell):
                                                mesh_th, truncation_psi, self.size)
 
     def render_colored_mesh(self, pose_to_camera, intrinsics, z, bone_length, voxel_size=0.003, mesh_th=15,
-                            truncation_psi=0.4, color="field", lit=True):
+                            truncation_psi=0.4, color="field", lit=True, normals="mesh"):
         """render_extracted_mesh in colour: the mesh carries the radiance field's colour at each vertex (color="field")
         or the colour of the part that owns it (color="parts", (semantic_palette + 1) / 2), drawn by the HIP rasteriser
         and the HIP deferred shading; `lit` keeps the hard-Phong terms. (image (512, 512, 3) uint8 numpy, (vertices,
-        triangles, colours (V, 3) fp32 or labels (V,) int32)); one sample, as render_mesh."""
+        triangles, colours (V, 3) fp32 or labels (V,) int32)); one sample, as render_mesh. normals="field" shades every
+        covered pixel with the field's own normal instead of the interpolated face normal."""
         z_nerf, z_render, _ = self._latent_parts(z)
         return self.nerf.render_colored_mesh(pose_to_camera, intrinsics, z_nerf, z_render, bone_length, voxel_size,
-                                             mesh_th, truncation_psi, self.size, color, lit)
+                                             mesh_th, truncation_psi, self.size, color, lit, normals)
 
     def render_mesh_turntable(self, pose_to_camera, intrinsics, z, bone_length, angles, voxel_size=0.003, mesh_th=15,
-                              truncation_psi=0.4, color="field", lit=True, render_size=512, simplify_cell=None):
+                              truncation_psi=0.4, color="field", lit=True, render_size=512, simplify_cell=None,
+                              normals="mesh"):
         """The coloured mesh of render_colored_mesh (simplified to cells of `simplify_cell` when given) on a turntable: (num, R, R, 3) uint8 frames on the device, frame i
         the mesh turned by angles[i] about the y axis through the mean joint translation (rotate_mesh_by_angle). The
         mesh and its colours or labels are extracted once; every angle is one rotate_mesh_by_angle, one rasterize_mesh
-        and one shade_fragments, with no host synchronisation inside. angles: num numbers or a (num,) tensor."""
+        and one shade_fragments, with no host synchronisation inside. angles: num numbers or a (num,) tensor.
+        normals="field" shades every covered pixel with the field's own normal: the pixel's surface point is turned back
+        into the extraction pose, the field's normal taken there (one gradient launch a frame) and turned with the mesh."""
         from .. import ops
-        from ..libraries.NARF.mesh_rendering import rasterize_mesh
+        from ..libraries.NARF.mesh_rendering import field_normals, rasterize_mesh
         from ..libraries.NARF.pose_utils import rotate_mesh_by_angle
         z_nerf, z_render, _ = self._latent_parts(z)
         vertices, triangles, _, how = self.nerf._colored_mesh(pose_to_camera, z_nerf, z_render, bone_length, voxel_size,
@@ -199,10 +213,24 @@ class TriNARFGenerator(_RendererShell):
         angles = torch.as_tensor(angles).to(device=dev, dtype=torch.float32).reshape(-1)
         frames = torch.empty((angles.shape[0], R, R, 3), dtype=torch.uint8, device=dev)
         pose = pose_to_camera.to(device=dev, dtype=torch.float32)
+        if normals not in ("mesh", "field"):
+            raise ValueError(f"normals is 'mesh' or 'field', got {normals!r}")
+        if normals == "field":
+            _, pose_parts, model_input = self.nerf.mesh_field(pose_to_camera, z_nerf, z_render, bone_length, truncation_psi)
         for i in range(angles.shape[0]):
             turned = rotate_mesh_by_angle(pose, (vertices,), angles[i:i + 1])[0].contiguous()
             f = rasterize_mesh(turned, triangles, intrinsics, self.size, R)
-            frames[i] = ops.shade_fragments(f.pix_to_face, f.bary, f.normals, turned, triangles, lit=lit, **how).image
+            shading = f.normals
+            if normals == "field":
+                # barycentrics are those of the turned mesh; the same mix of the unturned corners is the point the field knows
+                face = f.pix_to_face
+                points = (f.bary[..., None] * vertices[triangles[face.clamp(min=0)]]).sum(dim=-2).reshape(-1, 3)
+                n = field_normals(self.nerf, pose_parts, points, model_input)
+                ends = rotate_mesh_by_angle(pose, (points + n,), angles[i:i + 1])[0]
+                start = rotate_mesh_by_angle(pose, (points,), angles[i:i + 1])[0]
+                has = ((face >= 0).reshape(-1, 1)) & (n.abs().sum(dim=1, keepdim=True) > 0)
+                shading = torch.where(has, ends - start, f.normals.reshape(-1, 3)).reshape(f.normals.shape).contiguous()
+            frames[i] = ops.shade_fragments(f.pix_to_face, f.bary, shading, turned, triangles, lit=lit, **how).image
         return frames
 
     def extract_rigged_mesh(self, pose_to_camera, z, bone_length, voxel_size=0.003, mesh_th=15, truncation_psi=0.4,
@@ -227,15 +255,37 @@ class TriNARFGenerator(_RendererShell):
         return self.nerf.bake_texture(pose_to_camera, z_nerf, z_render, bone_length, vertices, triangles, truncation_psi,
                                       size, color, palette, color_fn, want_float)
 
+    def _passes_normals_on(render):
+        """Decorator of render_textured_mesh: adds the keyword normals = "mesh" (the method as it stands) or "field", which
+        goes to TriPlaneNARF.render_textured_mesh with the method's own arguments. The method keeps its signature."""
+        signature = inspect.signature(render)
+
+        @functools.wraps(render)
+        def wrapper(self, *args, normals="mesh", **kwargs):
+            if normals == "mesh":
+                return render(self, *args, **kwargs)
+            bound = signature.bind(self, *args, **kwargs)
+            bound.apply_defaults()
+            a = bound.arguments
+            z_nerf, z_render, _ = self._latent_parts(a["z"])
+            return self.nerf.render_textured_mesh(a["pose_to_camera"], a["intrinsics"], z_nerf, z_render, a["bone_length"],
+                                                  a["voxel_size"], a["mesh_th"], a["truncation_psi"], self.size,
+                                                  a["texture_size"], a["color"], a["lit"], a["simplify_cell"], normals=normals)
+        return wrapper
+
+    @_passes_normals_on
     def render_textured_mesh(self, pose_to_camera, intrinsics, z, bone_length, voxel_size=0.01, mesh_th=15,
                              truncation_psi=0.4, texture_size=1024, color="field", lit=True, simplify_cell=None):
         """render_colored_mesh with the colour in a texture atlas: a mesh coarse enough for other tools (voxel 0.01) keeps
         the field's colour detail. `simplify_cell` gets the coarse mesh from a fine extraction instead (a smaller
-        voxel_size, simplified to cells of simplify_cell). (image (512, 512, 3) uint8 numpy, (vertices, triangles, the
+        voxel_size, simplified to cells of simplify_cell). The keyword normals="field" (_passes_normals_on) shades every
+        covered pixel with the field's own normal. (image (512, 512, 3) uint8 numpy, (vertices, triangles, the
         TextureAtlas)); one sample."""
         z_nerf, z_render, _ = self._latent_parts(z)
         return self.nerf.render_textured_mesh(pose_to_camera, intrinsics, z_nerf, z_render, bone_length, voxel_size,
                                               mesh_th, truncation_psi, self.size, texture_size, color, lit, simplify_cell)
+
+    del _passes_normals_on                               # a decorator, not a method
 
     def render_textured_mesh_animation(self, rig, key_poses, bone_length, intrinsics, num=100, loop=True, orbit=None,
                                        lit=True, render_size=512, frames_per_batch=8):
@@ -357,20 +407,25 @@ class TriNARFGenerator(_RendererShell):
         return frames, part_maps, poses
 
     def render_geometry_animation(self, key_poses, bone_length, intrinsics, z, num=100, loop=True, orbit=None,
-                                  truncation_psi=0.4, frames_per_batch=8, background=1.0, shade="normal", **buffer_kwargs):
+                                  truncation_psi=0.4, frames_per_batch=8, background=1.0, shade="normal",
+                                  normals="stencil", **buffer_kwargs):
         """render_animation of the geometry: (frames (num, S, S, 3) uint8 - the shape image of ops.geometry_buffers in
         `shade` over `background` -, depth (num, S, S) fp32 in metric units, poses (num, J, 4, 4) in key_poses' dtype), all
         device tensors, with no host synchronisation inside. The structure is render_part_animation's: one
         interpolate_pose launch, one tri-plane, the frames marched frames_per_batch at a time, each chunk turned into
         bytes and depths by one geometry_buffers launch that writes into frames[a:b] and depth[a:b]; frames_per_batch=1
         gives the bytes of render_geometry on one frame. buffer_kwargs go to ops.geometry_buffers (edge, mask_threshold,
-        near, far, ...), except `want` and `out`, which this function sets itself: passing either raises ValueError."""
+        near, far, ...), except `want` and `out`, which this function sets itself: passing either raises ValueError.
+        normals="field" shades the frames with the field's own normals (render_geometry's keyword: a gradient launch and a
+        ray-normal launch a chunk more, the image copied into frames[a:b])."""
         from .. import ops
         from ..libraries.NeRF.rendering import render
         taken = sorted(k for k in ("want", "out") if k in buffer_kwargs)
         if taken:
             raise ValueError(f"render_geometry_animation writes image and depth into its own tensors: {', '.join(taken)} "
                              "cannot be passed")
+        if normals not in ("stencil", "field"):
+            raise ValueError(f"normals is 'stencil' or 'field', got {normals!r}")
         if not (z.shape[0] == 1 and bone_length.shape[0] == 1):
             raise AssertionError("render_geometry_animation takes one identity: z and bone_length of batch 1")
         per = int(frames_per_batch)
@@ -395,6 +450,12 @@ class TriNARFGenerator(_RendererShell):
                                           nerf.origin_location, nerf.coordinate_scale)
                 model_input = {"z": z_nerf, "z_rend": z_rend, "bone_length": bl, "truncation_psi": truncation_psi,
                                "tri_plane_feature": tri}
+                if normals == "field":
+                    buffers, _, _ = nerf.field_geometry(pixels[:c], K_inv.expand(c, -1, -1), parts, pack, model_input, (S, S),
+                                                        self._samples["Nc"], self._samples["Nf"], shade,
+                                                        background=background, **buffer_kwargs)
+                    frames[a:b], depth[a:b] = buffers.image, buffers.depth
+                    continue
                 _, alpha, disparity = render(nerf, pixels[:c], poses32.new_empty(c, nerf.num_bone, 4, 4),
                                              K_inv.expand(c, -1, -1), model_input=model_input, _parts=parts, _pack=pack,
                                              **self._samples)

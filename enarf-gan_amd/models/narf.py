@@ -15,6 +15,8 @@ callable with the calling convention `net(z, encoded_length, truncation_psi=...)
   * `deformation_field`:  `model.flow_generator` -> (B, 6, 256, 256) flow warping the constant feature planes (narf.py:39-58)
 or the caller passes `model_input["tri_plane_feature"]`.
 """
+import functools
+import inspect
 import math
 from typing import Dict, List, Optional, Union
 
@@ -23,6 +25,7 @@ import torch
 from torch import nn
 
 from .. import ops
+from ..libraries.NARF.mesh_rendering import _adds_return_normals
 from ..libraries.NARF.pose_utils import transform_pose
 from ..libraries.NeRF.utils import multi_part_positional_encoding
 from ..libraries.NeRF.rendering import _parts_from_part_poses, render, render_entire_img
@@ -329,13 +332,22 @@ class TriPlaneNARF(nn.Module):
 
     @torch.no_grad()
     def render_geometry(self, pose_to_camera, inv_intrinsics, z, z_rend, bone_length, size, truncation_psi=1, Nc=64, Nf=128,
-                        shade="normal", origin=(0, 0), step=1.0, camera_pose=None, **buffer_kwargs):
+                        shade="normal", origin=(0, 0), step=1.0, camera_pose=None, normals="stencil", min_gradient=0.0,
+                        bins=None, seed=None, **buffer_kwargs):
         """The geometry of the frames forward() renders: one march, then one launch of ops.geometry_buffers on the march's
         own disparity and mask. size = S or (H, W); pixel (r, c) is marched at x = origin[0] + (c + 0.5) step, y = origin[1] +
         (r + 0.5) step, the rule geometry_buffers applies to the same inv_intrinsics. Returns (image (B, H, W, 3) uint8,
         the GeometryBuffers, colour (B, 3, H, W), mask (B, H, W)). The disparity is brought back to metric units as
         TriNARFGenerator.forward does (x coordinate_scale, one fp32 multiply), so depth and points are in the space of
-        pose_to_camera and of extract_mesh's vertices, and equal geometry_buffers of forward's own outputs bit for bit."""
+        pose_to_camera and of extract_mesh's vertices, and equal geometry_buffers of forward's own outputs bit for bit.
+
+        normals="field" replaces the buffers' normals, flags and image by those of ops.ray_normals: the field's own normal of
+        every ray (minus the density gradient at the march's fine samples, composited with the march's weights; two
+        launches more), with the stencil normals as the fallback where the composited gradient does not exceed
+        `min_gradient`; bit 2 of the flags marks a field normal. Depth and points are geometry_buffers', untouched, and the
+        "depth" shade keeps its image. `bins` and `seed` are forward's."""
+        if normals not in ("stencil", "field"):
+            raise ValueError(f"normals is 'stencil' (depth differences) or 'field' (the density gradient), got {normals!r}")
         H, W = (int(size), int(size)) if not hasattr(size, "__len__") else (int(size[0]), int(size[1]))
         B, dev = pose_to_camera.shape[0], pose_to_camera.device
         idx = torch.arange(H * W, device=dev)
@@ -343,11 +355,41 @@ class TriPlaneNARF(nn.Module):
         y = (torch.div(idx, W, rounding_mode="floor") + 0.5).float() * step + origin[1]
         pixels = torch.stack([x, y, torch.ones_like(x)], dim=0)[None, None].expand(B, -1, -1, -1).contiguous()
         K_inv = torch.as_tensor(inv_intrinsics).float().to(dev)
+        if normals == "field":
+            parts, pack = ops.prepare(pose_to_camera, bone_length, self.canonical_bone_length, z_rend, self.mlp.as_dict(),
+                                      self.parent_id, self.origin_location, self.coordinate_scale)
+            model_input = {"z": z, "z_rend": z_rend, "bone_length": bone_length, "truncation_psi": truncation_psi}
+            buffers, color, mask = self.field_geometry(pixels, K_inv, parts, pack, model_input, (H, W), Nc, Nf, shade, origin,
+                                                       step, min_gradient, bins, seed, **buffer_kwargs)
+            return buffers.image, buffers, color.reshape(B, 3, H, W), mask.reshape(B, H, W)
         color, mask, disparity = self.forward(B, pixels, pose_to_camera, K_inv, z, z_rend, bone_length, Nc=Nc, Nf=Nf,
-                                              truncation_psi=truncation_psi, camera_pose=camera_pose, return_disparity=True)
+                                              truncation_psi=truncation_psi, camera_pose=camera_pose, return_disparity=True,
+                                              bins=bins, seed=seed)
         buffers = ops.geometry_buffers(disparity * self.coordinate_scale, mask, K_inv, size=(H, W), origin=origin, step=step,
                                        shade=shade, **buffer_kwargs)
         return buffers.image, buffers, color.reshape(B, 3, H, W), mask.reshape(B, H, W)
+
+    @torch.no_grad()
+    def field_geometry(self, pixels, K_inv, parts, pack, model_input, size, Nc, Nf, shade="normal", origin=(0, 0), step=1.0,
+                       min_gradient=0.0, bins=None, seed=None, **buffer_kwargs):
+        """render_geometry(normals="field") on prepared part records and MLP pack: one march with its taps, one
+        ops.field_gradient launch on its fine points, ops.geometry_buffers on the march's disparity and mask, one
+        ops.ray_normals launch with the stencil normals as the fallback -> (the GeometryBuffers with normals, flags and
+        image replaced, colour (B, 3, n), mask (B, n))."""
+        from ..libraries.NeRF.rendering import _march_with_gradient
+        taken = sorted(k for k in ("want", "out") if k in buffer_kwargs)
+        if taken:
+            raise ValueError(f"normals='field' takes every buffer of geometry_buffers: {', '.join(taken)} cannot be passed")
+        out, gradient = _march_with_gradient(self, pixels, K_inv, parts, pack, Nc, Nf, 1, model_input, bins, seed)
+        buffers = ops.geometry_buffers(out.disparity * self.coordinate_scale, out.mask, K_inv, size=size, origin=origin,
+                                       step=step, shade=shade, **buffer_kwargs)
+        keys = {k: buffer_kwargs[k] for k in ("mask_threshold", "background") if k in buffer_kwargs}
+        field = ops.ray_normals(gradient, out.fine_weights, out.mask.reshape(buffers.flags.shape), fallback=buffers.normals,
+                                flags=buffers.flags, points=buffers.points, shade=None if shade == "depth" else shade,
+                                min_gradient=min_gradient, **keys)
+        buffers = buffers._replace(normals=field.normals, flags=field.flags,
+                                   image=buffers.image if field.image is None else field.image)
+        return buffers, out.color, out.mask
 
     def density_volume(self, pose_to_camera, z, z_rend, bone_length, voxel_size=0.003, truncation_psi=0.4):
         """The (2/voxel_size + 1)^3 density grid `render_mesh` thresholds (libraries/NARF/base.py:65-77 up to the
@@ -356,13 +398,17 @@ class TriPlaneNARF(nn.Module):
         center, pose_parts, model_input = self._mesh_inputs(pose_to_camera, z, z_rend, bone_length, truncation_psi)
         return density_volume(self, pose_parts, center, voxel_size, model_input)
 
+    @_adds_return_normals(lambda a: a["self"].mesh_field(a["pose_to_camera"], a["z"], a["z_rend"], a["bone_length"],
+                                                         a["truncation_psi"]))
     def extract_mesh(self, pose_to_camera, z, z_rend, bone_length, voxel_size=0.003, mesh_th=15, truncation_psi=0.4,
                      return_part_labels=False, return_colors=False, simplify_cell=None):
         """The mesh of render_mesh / create_mesh built on the device: density sweep -> HIP marching cubes -> the
         reference's transform (mesh_rendering.extract_mesh). Returns (vertices (V, 3), triangles (T, 3) int64) and, with
         `return_part_labels`, (V,) int32 labels: the part that owns each vertex; with `return_colors`, (V, 3) fp32 in
         [0, 1]: the field's colour at each vertex (after the labels when both are asked for). `simplify_cell` = h
-        simplifies the mesh to cells of h straight after marching cubes (mesh_rendering.simplify_mesh)."""
+        simplifies the mesh to cells of h straight after marching cubes (mesh_rendering.simplify_mesh). The keyword
+        `return_normals` (mesh_rendering._adds_return_normals) adds, last, (V, 3) fp32 unit normals: the field's own normal
+        at each final vertex (one gradient launch)."""
         from ..libraries.NARF.mesh_rendering import extract_mesh
         center, pose_parts, model_input = self._mesh_inputs(pose_to_camera, z, z_rend, bone_length, truncation_psi)
         return extract_mesh(self, pose_parts, center, voxel_size, mesh_th, model_input, return_part_labels, return_colors,
@@ -389,23 +435,57 @@ class TriPlaneNARF(nn.Module):
         _, pose_parts, model_input = self._mesh_inputs(pose_to_camera, z, z_rend, bone_length, truncation_psi)
         return bake_texture(self, pose_parts, vertices, triangles, model_input, size, color, palette, color_fn, want_float)
 
-    def render_textured_mesh(self, pose_to_camera, intrinsics, z, z_rend, bone_length, voxel_size=0.01, mesh_th=15,
-                             truncation_psi=0.4, img_size=128, texture_size=1024, color="field", lit=True,
-                             simplify_cell=None):
-        """render_colored_mesh with the colour in a texture instead of on the vertices: extract_mesh (simplified to cells of
-        `simplify_cell` when that is given) -> bake_texture ->
-        paint_textured_mesh (HIP rasteriser, HIP textured shading, 512 x 512), one host copy of the finished image. The
-        colour resolution is the atlas's, not the mesh's: a coarse mesh keeps the field's detail. Returns (image
-        (512, 512, 3) uint8 numpy, (vertices, triangles, the TextureAtlas)); one sample."""
-        from ..libraries.NARF.mesh_rendering import bake_texture, extract_mesh, paint_textured_mesh
+    def _textured_mesh(self, pose_to_camera, z, z_rend, bone_length, voxel_size, mesh_th, truncation_psi, texture_size, color,
+                       simplify_cell):
+        """(vertices, triangles, the TextureAtlas, the `field` paint_textured_mesh(normals="field") takes) of
+        render_textured_mesh"""
+        from ..libraries.NARF.mesh_rendering import bake_texture, extract_mesh
         if color not in ("field", "parts"):
             raise ValueError(f"color is 'field' (the radiance field's colour) or 'parts' (the part labels), got {color!r}")
         center, pose_parts, model_input = self._mesh_inputs(pose_to_camera, z, z_rend, bone_length, truncation_psi)
         vertices, triangles = extract_mesh(self, pose_parts, center, voxel_size, mesh_th, model_input,
                                            simplify_cell=simplify_cell)
         atlas = bake_texture(self, pose_parts, vertices, triangles, model_input, texture_size, color)
+        return vertices, triangles, atlas, (self, pose_parts, model_input)
+
+    def _adds_field_shading(render):
+        """Decorator of render_textured_mesh: adds the keyword normals = "mesh" (the method as it stands) or "field" (every
+        covered pixel shaded with the field's own normal, paint_textured_mesh's keyword). The method keeps its signature."""
+        signature = inspect.signature(render)
+
+        @functools.wraps(render)
+        def wrapper(self, *args, normals="mesh", **kwargs):
+            if normals == "mesh":
+                return render(self, *args, **kwargs)
+            from ..libraries.NARF.mesh_rendering import paint_textured_mesh
+            bound = signature.bind(self, *args, **kwargs)
+            bound.apply_defaults()
+            a = bound.arguments
+            vertices, triangles, atlas, field = self._textured_mesh(
+                a["pose_to_camera"], a["z"], a["z_rend"], a["bone_length"], a["voxel_size"], a["mesh_th"], a["truncation_psi"],
+                a["texture_size"], a["color"], a["simplify_cell"])
+            _, painted = paint_textured_mesh(vertices, triangles, atlas, a["intrinsics"], a["img_size"], lit=a["lit"],
+                                             normals=normals, field=field)
+            return painted.image.cpu().numpy(), (vertices, triangles, atlas)
+        return wrapper
+
+    @_adds_field_shading
+    def render_textured_mesh(self, pose_to_camera, intrinsics, z, z_rend, bone_length, voxel_size=0.01, mesh_th=15,
+                             truncation_psi=0.4, img_size=128, texture_size=1024, color="field", lit=True,
+                             simplify_cell=None):
+        """render_colored_mesh with the colour in a texture instead of on the vertices: extract_mesh (simplified to cells of
+        `simplify_cell` when that is given) -> bake_texture ->
+        paint_textured_mesh (HIP rasteriser, HIP textured shading, 512 x 512), one host copy of the finished image. The
+        colour resolution is the atlas's, not the mesh's: a coarse mesh keeps the field's detail; the keyword
+        normals="field" (_adds_field_shading) shades every covered pixel with the field's own normal as well. Returns (image
+        (512, 512, 3) uint8 numpy, (vertices, triangles, the TextureAtlas)); one sample."""
+        from ..libraries.NARF.mesh_rendering import paint_textured_mesh
+        vertices, triangles, atlas, _ = self._textured_mesh(pose_to_camera, z, z_rend, bone_length, voxel_size, mesh_th,
+                                                            truncation_psi, texture_size, color, simplify_cell)
         _, painted = paint_textured_mesh(vertices, triangles, atlas, intrinsics, img_size, lit=lit)
         return painted.image.cpu().numpy(), (vertices, triangles, atlas)
+
+    del _adds_field_shading                              # a decorator, not a method
 
     def part_labels(self, points, pose_to_camera, z, bone_length, truncation_psi=1, points_last=False,
                     return_valid_bits=False):
@@ -445,17 +525,48 @@ class TriPlaneNARF(nn.Module):
         return vertices, triangles, paint, dict(vertex_labels=paint, palette=palette)
 
     def render_colored_mesh(self, pose_to_camera, intrinsics, z, z_rend, bone_length, voxel_size=0.003, mesh_th=15,
-                            truncation_psi=0.4, img_size=128, color="field", lit=True):
+                            truncation_psi=0.4, img_size=128, color="field", lit=True, normals="mesh"):
         """render_extracted_mesh in colour: extract_mesh with the field's colour at each vertex (color="field") or the
         part that owns it (color="parts", drawn in (semantic_palette + 1) / 2, a vertex no part owns in grey) ->
         paint_mesh (HIP rasteriser, HIP deferred shading, 512 x 512), one host copy of the finished image. `lit` keeps
-        the hard-Phong terms of render_extracted_mesh; without it the image is the colour itself. Returns (image
+        the hard-Phong terms of render_extracted_mesh; without it the image is the colour itself. normals="field" shades
+        every covered pixel with the field's own normal at its surface point (paint_mesh's keyword). Returns (image
         (512, 512, 3) uint8 numpy, (vertices, triangles, colours (V, 3) fp32 or labels (V,) int32)); one sample."""
         from ..libraries.NARF.mesh_rendering import paint_mesh
         vertices, triangles, paint, how = self._colored_mesh(pose_to_camera, z, z_rend, bone_length, voxel_size, mesh_th,
                                                              truncation_psi, color)
-        _, painted = paint_mesh(vertices, triangles, intrinsics, img_size, lit=lit, **how)
+        _, painted = paint_mesh(vertices, triangles, intrinsics, img_size, lit=lit, normals=normals,
+                                field=self.mesh_field(pose_to_camera, z, z_rend, bone_length, truncation_psi)
+                                if normals == "field" else None, **how)
         return painted.image.cpu().numpy(), (vertices, triangles, paint)
+
+    def mesh_field(self, pose_to_camera, z, z_rend, bone_length, truncation_psi=0.4):
+        """(model, part frames, model_input): the `field` paint_mesh(normals="field") and mesh_rendering.field_normals take
+        for a mesh extracted with these arguments"""
+        _, pose_parts, model_input = self._mesh_inputs(pose_to_camera, z, z_rend, bone_length, truncation_psi)
+        return self, pose_parts, model_input
+
+    def field_gradient(self, points: torch.Tensor, pose_to_camera: torch.Tensor, model_input: Dict):
+        """The density and its spatial gradient at points: (density (B, n), gradient (B, 3, n)) of ops.field_gradient, one
+        launch. Arguments as calc_density_and_color_from_camera_coord_v2 takes them: points (B, 3, n) camera coords and
+        pose_to_camera (B, P, 4, 4) part frames, both already x coordinate_scale; model_input["bone_length"] the parts'
+        bone lengths. The surface normal is -gradient / |gradient|. Runs under no_grad; nothing here is differentiable:
+        an input that requires a gradient raises NotImplementedError."""
+        if torch.is_grad_enabled() and (points.requires_grad or pose_to_camera.requires_grad or
+                                        model_input["bone_length"].requires_grad or model_input["z_rend"].requires_grad or
+                                        self._tri_plane_graph(model_input).requires_grad or
+                                        any(p.requires_grad for p in self.mlp.as_dict().values())):
+            raise NotImplementedError("field_gradient carries no gradient (normals are not differentiable); call it under "
+                                      "torch.no_grad()")
+        with torch.no_grad():
+            B, P = pose_to_camera.shape[:2]
+            parts = torch.zeros(B, P, 16, dtype=torch.float32, device=points.device)
+            parts[:, :, :9] = pose_to_camera[:, :, :3, :3].reshape(B, P, 9)
+            parts[:, :, 9:12] = pose_to_camera[:, :, :3, 3]
+            parts[:, :, 12] = (self.canonical_bone_length[:, None] / model_input["bone_length"] / self.coordinate_scale)[:, :, 0]
+            tri, feat_cl = self._tri_plane_pair(model_input)
+            return ops.field_gradient(points.float(), parts, self.canonical_pose, tri, feat_cl,
+                                      self._mlp_pack(model_input["z_rend"]), **self.kernel_flags())
 
     def _mesh_inputs(self, pose_to_camera, z, z_rend, bone_length, truncation_psi):
         if not ((z is None or z.shape[0] == 1) and (bone_length is None or bone_length.shape[0] == 1)):

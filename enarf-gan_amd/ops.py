@@ -1087,6 +1087,43 @@ def geometry_buffers(disparity: torch.Tensor, mask: torch.Tensor, inv_intrinsics
                                       normalise, shade, near, far, background, want, out)
 
 
+# ------------------------------------------------------------------------------------------------- field normals
+from ._nrm_lib import RayNormals  # noqa: E402,F401  (ray_normals' result)
+
+
+def field_gradient(points: torch.Tensor, parts: torch.Tensor, canonical_pose: torch.Tensor, tri_nchw: torch.Tensor,
+                   feat_cl: torch.Tensor, mlp_pack: torch.Tensor, clamp_mask: bool = False, uniform_part_weight: bool = False,
+                   multiply_density_with_weight: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The density of query_fwd (mode f32) and its spatial gradient, in one launch of libenarf_nrm.so: (density (B, N),
+    gradient (B, 3, N)) fp32, the gradient in the space the points are given in (the scaled camera space). Arguments as
+    query_pose_bwd takes them, without upstream gradients. The gradient is query_pose_bwd's g_points for g_density = 1 and
+    g_color = None - what the reference's autograd returns for sum(density): zero where the density head is off, validity
+    and the bilinear cells constants - without the colour head, the record gradients and the second launch. A point in no
+    cube gets density 0 and an exact zero gradient. The surface normal is -gradient / |gradient|. No atomics:
+    bit-identical from run to run; nothing synchronises; N = 0 launches nothing. ValueError for shapes it does not take."""
+    from . import _nrm_lib
+    return _nrm_lib.field_gradient(points, parts, canonical_pose, tri_nchw, feat_cl, mlp_pack, clamp_mask, uniform_part_weight,
+                                   multiply_density_with_weight)
+
+
+def ray_normals(gradient: torch.Tensor, weights: torch.Tensor, mask: torch.Tensor, *, fallback: Optional[torch.Tensor] = None,
+                flags: Optional[torch.Tensor] = None, points: Optional[torch.Tensor] = None, shade: Optional[str] = None,
+                mask_threshold=0.5, min_gradient=0.0, background=1.0, want_magnitude: bool = False) -> RayNormals:
+    """The field normal of every ray of a march, in one launch of libenarf_nrm.so: the namedtuple RayNormals (normals
+    (B, n, 3) fp32, flags (B, n) uint8, magnitude (B, n) fp32 or None, image (B, n, 3) uint8 or None). gradient (B, 3, n Nf)
+    from field_gradient at the march's fine points (ray-major, sample-minor), weights the march's fine_weights (B, n,
+    Nf - 1) or (B, 1, n, Nf - 1) - weight i belongs to sample i, as in composite_fine -, mask (B, n), or (B, H, W) for
+    outputs of that shape. G = sum_i w_i g_i over the first Nf - 1 samples in ascending order, m = |G|; a ray has a field
+    normal -G / m when mask >= mask_threshold and m > min_gradient; otherwise it takes `fallback` (B, n, 3) where bit 1 of
+    `flags` (B, n) uint8 is set - the normals and flags geometry_buffers returns - or zeros. The flags returned keep the
+    given bits and set bit 2 on a field normal. `shade` = "normal" or "lit" adds the 8-bit image in geometry_buffers'
+    formulas over `background` ("lit" takes `points` (B, n, 3)); `want_magnitude` adds m. Computed in fp64 from the fp32
+    inputs, bit-identical from run to run, nothing synchronises. NotImplementedError for Nf outside [2, 128] or B above
+    65535, ValueError for shapes, dtypes or values it does not take."""
+    from . import _nrm_lib
+    return _nrm_lib.ray_normals(gradient, weights, mask, fallback, flags, points, shade, mask_threshold, min_gradient,
+                                background, want_magnitude)
+
 
 # ------------------------------------------------------------------------------------------------- multi-avatar scenes
 from ._scene_lib import SceneComposite  # noqa: E402,F401  (scene_composite's result)

@@ -22,6 +22,8 @@ extracts the mesh of the first key once (HIP marching cubes), in the radiance fi
 turns it through `--num` angles of one turn (render_mesh_turntable: HIP rasteriser and deferred shading per frame).
 `--geometry normal|lit|depth` draws the shape the march itself carries - the normal map, a lit white surface, or the
 inverse depth between `--depth-range` - from the disparity of each frame (ops.geometry_buffers, no mesh extracted).
+`--normals field` shades `--geometry` and `--mesh-turntable` with the field's own normals, minus the density gradient
+(libenarf_nrm.so), instead of the depth stencil's or the mesh faces'.
 `--skinned-mesh field|parts|white` extracts the mesh of the first key once, binds it to the model's parts
 (extract_rigged_mesh: `--influences` 4 or 8 a vertex) and moves it through the key poses by linear-blend skinning
 (render_mesh_animation: one skin_pose launch a chunk, HIP rasteriser and deferred shading per frame); `--export-glb PATH`
@@ -62,6 +64,9 @@ def main():
     ap.add_argument("--geometry", choices=["normal", "lit", "depth"], default=None,
                     help="the shape image of the march's depth in place of the colour")
     ap.add_argument("--depth-range", default="1.0,5.0", help="--geometry depth: near,far in the poses' units")
+    ap.add_argument("--normals", choices=["default", "field"], default="default",
+                    help="--geometry and --mesh-turntable: 'field' shades with the field's own normals (the density "
+                         "gradient) instead of the depth stencil's or the mesh faces'")
     ap.add_argument("--mesh-turntable", choices=["field", "parts"], default=None,
                     help="a turntable of the first key's coloured mesh in place of the march")
     ap.add_argument("--skinned-mesh", choices=["field", "parts", "white", "texture"], default=None,
@@ -145,12 +150,14 @@ def main():
         frames = gen.render_mesh_turntable(key_poses[:1].float(), intrinsics, z, bone_length, angles,
                                            voxel_size=args.voxel_size, mesh_th=args.mesh_th,
                                            truncation_psi=args.truncation_psi, color=args.mesh_turntable,
-                                           lit=not args.unlit, render_size=args.render_size, simplify_cell=args.simplify)
+                                           lit=not args.unlit, render_size=args.render_size, simplify_cell=args.simplify,
+                                           normals="field" if args.normals == "field" else "mesh")
     elif args.geometry:
         near, far = (float(v) for v in args.depth_range.split(","))
         frames, _, _ = gen.render_geometry_animation(key_poses, bone_length, intrinsics, z, num=args.num,
                                                      loop=not args.no_loop, orbit=orbit, truncation_psi=args.truncation_psi,
                                                      frames_per_batch=args.frames_per_batch, shade=args.geometry,
+                                                     normals="field" if args.normals == "field" else "stencil",
                                                      near=near, far=far)
     elif args.parts:
         frames, _, _ = gen.render_part_animation(key_poses, bone_length, intrinsics, z, num=args.num, loop=not args.no_loop,

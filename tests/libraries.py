@@ -34,7 +34,7 @@ def library(stem):
 
 
 def header(stem):
-    return os.path.join(ROOT, "include", build.LIBRARIES[stem][1])
+    return os.path.join(ROOT, "include", build.ALL_LIBRARIES[stem][1])      # rows of either table
 
 
 def binding(stem):

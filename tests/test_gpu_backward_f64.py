@@ -204,14 +204,18 @@ def test_render_bwd_drop_invalid_rays_forced():
 
 
 # ------------------------------------------------------------------------------------------ query_bwd on placed points
-@pytest.mark.parametrize("modes", [{}, dict(multiply_density_with_weight=True, clamp_mask=True)])
-def test_query_bwd_placed_points_vs_float64(modes):
-    from enarf_gan_amd import ops
+_QUERY_BWD = {}
+
+
+def query_bwd_case(modes):
+    """the scene, placed points, upstream gradients and float64 / fp32 autograd gradients of the query: once per flag set"""
+    key = tuple(sorted(modes.items()))
+    if key in _QUERY_BWD:
+        return _QUERY_BWD[key]
     sc = Scene(32, 2, "center_fixed", 20)
     if modes.get("clamp_mask"):
         sc.raw["tri_plane"] = sc.raw["tri_plane"].clone()
         sc.raw["tri_plane"][:, 96:] *= 3.0
-    ds = DeviceScene(sc)
     H, W = sc.raw["tri_plane"].shape[2:]
     pts = torch.stack([_query_points(sc, b, H, W) for b in range(2)]).contiguous()
     N = pts.shape[-1]
@@ -235,16 +239,30 @@ def test_query_bwd_placed_points_vs_float64(modes):
                               O.modulated_weights(mlp, z), **modes)
         gr = torch.autograd.grad((den * gD.to(dt)).sum() + (col * gC.to(dt)).sum(), [tri, z] + [mlp[q] for q in R.LEAVES])
         grads[dt] = {"feat": gr[0][:, :96], "mask": gr[0][:, 96:], "z": gr[1], **dict(zip(R.LEAVES, gr[2:]))}
+    _QUERY_BWD[key] = (sc, pts, gD, gC, {"g64": grads[torch.float64], "g32": grads[torch.float32]})
+    return _QUERY_BWD[key]
+
+
+def query_bwd_grads(ds, pts_d, gD_d, gC_d, modes):
+    """enarf_query_bwd (+ enarf_weight_grad) + enarf_prepare_bwd -> {"feat", "mask", "z", *LEAVES} on the device"""
+    from enarf_gan_amd import ops
     kflags = dict(multiply_density_with_weight=modes.get("multiply_density_with_weight", False),
                   clamp_mask=modes.get("clamp_mask", False))
-    grad_tri, dW, db = ops.query_bwd(pts.cuda(), ds.parts, ds.cpose, ds.tri, ds.feat_cl, ds.pack, gD.cuda(), gC.cuda(), **kflags)
-    pg, dz = ops.prepare_bwd(sc.raw["z_rend"].cuda(), ds.mlp, dW)
+    grad_tri, dW, db = ops.query_bwd(pts_d, ds.parts, ds.cpose, ds.tri, ds.feat_cl, ds.pack, gD_d, gC_d, **kflags)
+    pg, dz = ops.prepare_bwd(ds.sc.raw["z_rend"].to(ds.dev), ds.mlp, dW)
     ours = {"feat": grad_tri[:, :96], "mask": grad_tri[:, 96:], "z": dz}
     for l in range(3):
         ours[f"layers.{l}.bias"] = db[l]
         for leaf in ("conv.weight", "conv.modulation.weight", "conv.modulation.bias"):
             ours[f"layers.{l}.{leaf}"] = pg[f"layers.{l}.{leaf}"]
-    ratios = R.check_grads(ours, {"g64": grads[torch.float64], "g32": grads[torch.float32]}, f"query_bwd {modes}")
+    return ours
+
+
+@pytest.mark.parametrize("modes", [{}, dict(multiply_density_with_weight=True, clamp_mask=True)])
+def test_query_bwd_placed_points_vs_float64(modes):
+    sc, pts, gD, gC, ref = query_bwd_case(modes)
+    ours = query_bwd_grads(DeviceScene(sc), pts.cuda(), gD.cuda(), gC.cuda(), modes)
+    ratios = R.check_grads(ours, ref, f"query_bwd {modes}")
     print(f"query_bwd {modes}: " + ", ".join(f"{k} {v:.3f}" for k, v in ratios.items()))
 
 

@@ -63,6 +63,19 @@ def _sphere_atlas(kind):
 
 
 # ------------------------------------------------------------------------------------------------- the kernels alone
+def _check_points(got, ref, A, what):
+    """bake_points' two outputs (numpy) against bake_reference.points' -> the map of owned texels"""
+    assert got["points"].shape == (3, A * A) and got["points"].dtype == np.float32
+    assert got["texel_face"].shape == (A, A) and got["texel_face"].dtype == np.int32
+    assert np.array_equal(got["texel_face"], ref["texel_face"])
+    u = BR.ulps_from(got["points"], ref["points"])
+    own = ref["texel_face"] >= 0
+    print(f"{what}: {own.sum()} owned texels of {own.size}, points {u.max():.0f} ulp ({(u > 0).sum()} values off)")
+    assert u.max() <= 1
+    assert (got["points"].reshape(3, A, A)[:, ~own] == 0).all()
+    return own
+
+
 @pytest.mark.parametrize("case", [(1, 6), (5, 16), (5, 21), (8, 12), "sphere"])
 def test_bake_points_match_the_referee_on_every_texel(case):
     """texel_face equal, points the referee rounded to fp32 or one step from it. (5, .) is the hand mesh whose triangle 3
@@ -75,14 +88,7 @@ def test_bake_points_match_the_referee_on_every_texel(case):
     else:
         assert BR.layout(len(t), A)[0] == BC.LAYOUTS[case]
     got, ref = _points(v, t, A), BR.points(v, t, A)
-    assert got["points"].shape == (3, A * A) and got["points"].dtype == np.float32
-    assert got["texel_face"].shape == (A, A) and got["texel_face"].dtype == np.int32
-    assert np.array_equal(got["texel_face"], ref["texel_face"])
-    u = BR.ulps_from(got["points"], ref["points"])
-    own = ref["texel_face"] >= 0
-    print(f"{case}: {own.sum()} owned texels of {own.size}, points {u.max():.0f} ulp ({(u > 0).sum()} values off)")
-    assert u.max() <= 1
-    assert (got["points"].reshape(3, A, A)[:, ~own] == 0).all()
+    own = _check_points(got, ref, A, case)
     owned = set(np.unique(ref["texel_face"][own]).tolist())
     assert owned == (set(range(len(t))) - {3, 4} if case in ((5, 16), (5, 21)) else set(range(len(t))))
 
@@ -95,6 +101,14 @@ def test_bands_of_rows_stitch_to_the_whole_atlas():
             assert band["points"].shape == (3, (b - a) * A) and band["texel_face"].shape == (b - a, A)
         assert np.concatenate([b["texel_face"] for b in bands]).tobytes() == whole["texel_face"].tobytes()
         assert np.concatenate([b["points"] for b in bands], axis=1).tobytes() == whole["points"].tobytes()
+
+
+def _check_resolved(tex, f32, ref, face, what):
+    """bake_resolve's texture (and its fp32 texture, or None) as numpy against bake_reference.resolve's"""
+    assert tex.shape == face.shape + (4,) and tex.dtype == np.uint8 and (f32 is None or f32.shape == face.shape + (3,))
+    u = np.zeros(1) if f32 is None else BR.ulps_from(f32, ref["texture_f32"])
+    print(f"{what}: {(tex != ref['texture']).sum()} bytes differ, fp32 texture {u.max():.0f} ulp")
+    assert np.array_equal(tex, ref["texture"]) and u.max() <= 1
 
 
 def test_bake_resolve_matches_the_referee():
@@ -110,10 +124,7 @@ def test_bake_resolve_matches_the_referee():
         torch.cuda.synchronize()
         ref = BR.resolve(face, **data, fill=fill, **kw)
         tex, f32 = _np(out.texture), _np(out.texture_f32)
-        assert tex.shape == face.shape + (4,) and tex.dtype == np.uint8 and f32.shape == face.shape + (3,)
-        u = BR.ulps_from(f32, ref["texture_f32"])
-        print(f"{what}: {(tex != ref['texture']).sum()} bytes differ, fp32 texture {u.max():.0f} ulp")
-        assert np.array_equal(tex, ref["texture"]) and u.max() <= 1
+        _check_resolved(tex, f32, ref, face, what)
         empty = face < 0
         assert empty.sum() > 5 and (tex[empty] == [51, 102, 153, 0]).all() and (tex[~empty][:, 3] == 255).all()
         assert (f32[empty] == np.float32(fill)).all()

@@ -157,6 +157,13 @@ def test_query_fwd_placed_points_vs_float64(ops, clamp, mode):
     ds = DeviceScene(sc)
     den, col, vb, dc, dw = ds.query(pts, mlp_mode=mode, debug=True, **modes)
     torch.cuda.synchronize()
+    worst = check_query(den, col, vb, dc, dw, clamp, mode)
+    print(f"query_fwd {mode} {modes}: worst error / bound per tensor: {FR.fmt(worst)}")
+
+
+def check_query(den, col, vb, dc, dw, clamp, mode):
+    """the outputs of query_fwd(debug=True) on _query_ref(clamp)'s points against its referee -> worst error / bound per tensor"""
+    sc, pts, modes, t64, t32, draws, keep, v32 = _query_ref(clamp)
     assert np.array_equal(vb.cpu().numpy().view(np.uint32), bits_of(v32)), "validity bit masks differ from the oracle's"
     ours = _query_tensors(den, col, dw, dc)
     in_a_part = v32.any(1).numpy()
@@ -172,4 +179,4 @@ def test_query_fwd_placed_points_vs_float64(ops, clamp, mode):
         i = np.unravel_index(int(np.argmax(rt)), rt.shape)
         assert worst[k] <= 1.0, (f"query {mode} {modes}: {k}: entry {tuple(int(j) for j in i)} is {worst[k]:.3g}x its bound, "
                                  f"{int((rt > 1).sum())} above; ours {ours[k][i]} float64 {t64[k][i]} fp32 {t32[k][i]}")
-    print(f"query_fwd {mode} {modes}: worst error / bound per tensor: {FR.fmt(worst)}")
+    return worst

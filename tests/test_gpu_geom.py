@@ -143,6 +143,15 @@ def _ulp32(got, ref):
     return float(GR.ulps_from(np.float32(got), np.float64(ref)))
 
 
+def _check_depth_error(got, ref, shape):
+    """DepthError.result() after two updates of `shape` against the merged referee: counts exact, sums to one fp32 ulp"""
+    for k in ("n", "n_fg", "inter", "union"):
+        assert got[k] == ref[k], k
+    assert got["updates"] == 2 and got["n"] == 2 * int(np.prod(shape))
+    for k in ("sse_all", "sse_fg"):
+        assert _ulp32(got[k], ref[k]) <= 1, (k, got[k], ref[k])
+
+
 @pytest.mark.parametrize("shape", [(3, 37, 53), (1, 1, 1)])
 @pytest.mark.parametrize("with_mask", [True, False])
 def test_depth_error_matches_the_referee_and_repeats_bit_for_bit(shape, with_mask):
@@ -162,11 +171,7 @@ def test_depth_error_matches_the_referee_and_repeats_bit_for_bit(shape, with_mas
     err, bits = run()
     got = err.result()
     print(f"depth error {shape} mask={with_mask}: {got}")
-    for k in ("n", "n_fg", "inter", "union"):
-        assert got[k] == ref[k], k
-    assert got["updates"] == 2 and got["n"] == 2 * int(np.prod(shape))
-    for k in ("sse_all", "sse_fg"):
-        assert _ulp32(got[k], ref[k]) <= 1, (k, got[k], ref[k])
+    _check_depth_error(got, ref, shape)
     assert got["inv_depth_mse"] == got["sse_all"] / got["n"] and _ulp32(got["inv_depth_mse"], ref["inv_depth_mse"]) <= 1
     assert got["iou"] == got["inter"] / got["union"] if got["union"] else np.isnan(got["iou"])
     assert run()[1] == bits

@@ -106,6 +106,24 @@ def test_two_runs_give_equal_bits():
 
 
 # ------------------------------------------------------------------------------------------------- the ray kernel
+def _check_ray_normals(got, ref, n, shade, what):
+    """a RayNormals (B = 2) against nrm_reference.ray_normals' dict; the magnitude unless the call left it out (`magnitude`
+    None), the image when `shade` is given"""
+    assert got.normals.shape == (2, n, 3) and got.flags.dtype == torch.uint8
+    assert np.array_equal(got.flags.cpu().numpy(), ref["flags"]), what
+    un = GR.ulps_from(got.normals.cpu().numpy(), ref["normals"])
+    um = np.zeros(1) if got.magnitude is None else GR.ulps_from(got.magnitude.cpu().numpy(), ref["magnitude"])
+    assert got.magnitude is None or got.magnitude.shape == (2, n)
+    print(f"{what}: normals {un.max():.0f} ulp ({(un > 0).sum()} off), magnitude {um.max():.0f} ulp, "
+          f"{int((ref['flags'] & 4 > 0).sum())} of {2 * n} field normals")
+    assert un.max() <= 1 and um.max() <= 1, what
+    if shade is None:
+        assert got.image is None
+        return
+    d = np.abs(got.image.cpu().numpy().astype(np.int16) - ref["image"].astype(np.int16))
+    assert got.image.dtype == torch.uint8 and d.max() <= 1, what
+
+
 @pytest.mark.parametrize("n,Nf", NR.RAY_CASES)
 def test_ray_normals_match_the_referee(n, Nf):
     """B = 2 on nrm_reference.ray_case's inputs: rays with all-zero weights, a zero gradient, a mask below the threshold and
@@ -118,18 +136,8 @@ def test_ray_normals_match_the_referee(n, Nf):
     for kw in (dict(shade="normal"), dict(shade="lit", background=(0.1, 0.2, 0.3)), dict(shade=None, mask_threshold=0.05)):
         got = _ray_kernel(c, **kw)
         ref = NR.ray_normals(c["gradient"], c["weights"], c["mask"], c["fallback"], c["flags"], c["points"], **kw)
-        what = f"n = {n}, Nf = {Nf}, {kw}"
-        assert got.normals.shape == (2, n, 3) and got.flags.dtype == torch.uint8 and got.magnitude.shape == (2, n)
-        assert np.array_equal(got.flags.cpu().numpy(), ref["flags"]), what
-        un, um = GR.ulps_from(got.normals.cpu().numpy(), ref["normals"]), GR.ulps_from(got.magnitude.cpu().numpy(), ref["magnitude"])
-        print(f"{what}: normals {un.max():.0f} ulp ({(un > 0).sum()} off), magnitude {um.max():.0f} ulp, "
-              f"{int((ref['flags'] & 4 > 0).sum())} of {2 * n} field normals")
-        assert un.max() <= 1 and um.max() <= 1, what
-        if kw["shade"] is None:
-            assert got.image is None
-            continue
-        d = np.abs(got.image.cpu().numpy().astype(np.int16) - ref["image"].astype(np.int16))
-        assert got.image.dtype == torch.uint8 and d.max() <= 1, what
+        assert got.magnitude is not None
+        _check_ray_normals(got, ref, n, kw["shade"], f"n = {n}, Nf = {Nf}, {kw}")
     field = (ref["flags"] & 4) > 0                           # the last setting: every mask passes, so the kinds decide
     assert np.array_equal(field, np.isin(c["kind"], (0, 3, 4)))
     # without a fallback the same rays have a field normal and the others are zeros

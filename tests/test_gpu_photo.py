@@ -178,8 +178,13 @@ def _blob_images(B, H, W, rng):
 
 def _check_metrics(img, gen, mask, gen_mask, bbox, what):
     from enarf_gan_amd import ops
-    out = ops.image_metrics(_dev(img), _dev(gen), _dev(mask), _dev(gen_mask), bbox=bbox)
-    assert out.shape == (len(img), 4) and out.dtype == torch.float32 and out.is_cuda
+    return _check_metric_values(ops.image_metrics(_dev(img), _dev(gen), _dev(mask), _dev(gen_mask), bbox=bbox), img, gen, mask,
+                                gen_mask, bbox, what)
+
+
+def _check_metric_values(out, img, gen, mask, gen_mask, bbox, what):
+    """the (B, 4) result of image_metrics on these host arrays against the referee"""
+    assert out.shape == (len(img), 4) and out.dtype == torch.float32
     out = out.cpu().numpy().astype(np.float64)
     boxes = [None] * len(img) if bbox is None else ([bbox] * len(img) if not hasattr(bbox[0], "__len__") else bbox)
     worst = 0.0

@@ -1,5 +1,5 @@
-"""Build recipe of the HIP libraries (hipcc, gfx950 only), in-tree under csrc/: the tables LIBRARIES and SIDE_LIBRARIES below
-are the one place a library is declared, one libenarf_<stem>.so per row.
+"""Build recipe of the HIP libraries (hipcc, gfx950 only), in-tree under csrc/: the tables LIBRARIES, SIDE_LIBRARIES and
+LATE_LIBRARIES below are the one place a library is declared, one libenarf_<stem>.so per row.
 
 `python -m enarf_gan_amd.build` or `build()`; `__graft_entry__.build()` calls this. The .so files are
 git-ignored but travel to the GPU box with the repo snapshot. `python -m enarf_gan_amd.build --variant NAME [-DFLAG=V ...]`
@@ -8,7 +8,9 @@ is what tools/build_variant.sh runs: a second build of libenarf_hip.so under var
 Adding a library: a row, its public header under include/, a binding module `_<stem>_lib.py` (constants, SIGNATURES, a
 `_loader.Library`, the ops) and a kernel -> GPU tests map. Rows of LIBRARIES have their maps in tests/kernel_coverage.py and
 are checked by tests/test_libraries_cpu.py (ABI, inventory, disjointness, header tracking); rows of SIDE_LIBRARIES have a
-registry module each (tests/<stem>_kernel_coverage.py) and get the same checks from tests/test_side_libraries_cpu.py.
+registry module each (tests/<stem>_kernel_coverage.py) and get the same checks from tests/test_side_libraries_cpu.py; a row
+of LATE_LIBRARIES brings its registry module, the same checks and its poison cases in test files of its own
+(tests/test_<stem>_cpu.py, tests/<stem>_poison_cases.py).
 """
 from __future__ import annotations
 
@@ -49,6 +51,15 @@ SIDE_LIBRARIES = {
     "skin": (["enarf_skin.hip"], "enarf_skin.h"),          # skin weights of mesh vertices, linear-blend posing of the mesh
 }
 ALL_LIBRARIES = {**LIBRARIES, **SIDE_LIBRARIES}
+# Libraries added after the tests of the two tables above were bound to them (tests/test_skin_cpu.py names the last side
+# row, tests/poison_cases.py holds a case for every function of every row of ALL_LIBRARIES, and both files stay as they
+# are): the move that created SIDE_LIBRARIES, made once more. Same recipe, same binding conventions, built and loaded with
+# the rest; each row brings, in test files of its own, its registry (tests/<stem>_kernel_coverage.py), the per-row checks
+# of tests/test_side_libraries_cpu.py (tests/test_<stem>_cpu.py) and its poison cases (tests/<stem>_poison_cases.py).
+LATE_LIBRARIES = {
+    "nmap": (["enarf_nmap.hip"], "enarf_nmap.h"),          # tangent-space normal maps in the atlas: encode, normal-mapped shade
+}
+EVERY_LIBRARY = {**ALL_LIBRARIES, **LATE_LIBRARIES}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
          "-I", os.path.join(ROOT, "include"), "-I", CSRC]
 
@@ -67,7 +78,7 @@ def lib_deps(stem: str) -> list:
     enarf_tasks.h was added), include/enarf_hip.h, the row's own public header and this file."""
     include = os.path.join(ROOT, "include")
     return ([os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h")] +
-            [os.path.join(include, "enarf_hip.h"), os.path.join(include, ALL_LIBRARIES[stem][1]), os.path.abspath(__file__)])
+            [os.path.join(include, "enarf_hip.h"), os.path.join(include, EVERY_LIBRARY[stem][1]), os.path.abspath(__file__)])
 
 
 LIB = lib_path("hip")
@@ -112,9 +123,9 @@ def _make(targets, force, verbose, extra_flags) -> None:
 
 
 def build(force: bool = False, verbose: bool = False, extra_flags=()) -> str:
-    """Build every library of LIBRARIES and SIDE_LIBRARIES incrementally; returns the path of libenarf_hip.so (the others
+    """Build every library of LIBRARIES, SIDE_LIBRARIES and LATE_LIBRARIES incrementally; returns the path of libenarf_hip.so (the others
     are next to it, at lib_path(stem))."""
-    _make([(lib_path(stem), CSRC, sources, lib_deps(stem)) for stem, (sources, _) in ALL_LIBRARIES.items()],
+    _make([(lib_path(stem), CSRC, sources, lib_deps(stem)) for stem, (sources, _) in EVERY_LIBRARY.items()],
           force, verbose, extra_flags)
     return LIB
 

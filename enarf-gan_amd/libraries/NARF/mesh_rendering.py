@@ -382,14 +382,62 @@ def bake_texture(model, pose_to_camera, vertices: torch.Tensor, triangles: torch
     return TextureAtlas(texture, texture_f32, T, A, lay.cell)
 
 
+@torch.no_grad()
+def bake_normal_map(model, pose_to_camera, vertices: torch.Tensor, triangles: torch.Tensor, model_input: Dict = {},
+                    size: int = 1024, normal_fn=None, min_gradient: float = 0.0, want_float: bool = False,
+                    band_rows: Optional[int] = None) -> TextureAtlas:
+    """The tangent-space normal map of a mesh in the atlas of bake_texture (the same layout: a TextureAtlas whose texture
+    holds normals, texture_f32 them unquantised with `want_float`): band of rows by band as there, ops.bake_points gives
+    the surface point of every texel, one ops.field_gradient launch a band the density's gradient there with the scaling
+    and flags of field_normals, and ops.encode_normal_map writes -gradient / |gradient| in the frame of the texel's
+    triangle (include/enarf_nmap.h) into the band's rows; a texel whose |gradient| <= min_gradient is flat (the face
+    normal). A band the layout leaves without an owned texel is filled with the empty texel and skipped. With `normal_fn`,
+    a function points (M, 3) -> vectors (M, 3), the vectors are the normals themselves and the model may be None. The map
+    is baked in the pose the vertices are in - the rest pose of a rig - and rides with the triangles through skin_mesh:
+    the frame is rebuilt from the posed vertices when it is drawn. Nothing synchronises."""
+    T, A = triangles.shape[0], int(size)
+    lay = ops.bake_layout(T, A)
+    dev = vertices.device
+    texture = torch.empty(A, A, 4, dtype=torch.uint8, device=dev)
+    texture_f32 = torch.empty(A, A, 3, dtype=torch.float32, device=dev) if want_float else None
+    per = max(1, min(A, (1 << 22) // A)) if band_rows is None else max(1, int(band_rows))
+    if normal_fn is None:
+        from ..NeRF.rendering import _parts_from_part_poses
+        cs = model.coordinate_scale
+        flags = model.kernel_flags()
+        parts = _parts_from_part_poses(model, pose_to_camera, model_input["bone_length"])
+        tri, feat_cl = model._tri_plane_pair(model_input)
+        pack = model._mlp_pack(model_input["z_rend"])
+    for a in range(0, A, per):
+        b = min(a + per, A)
+        out = (texture[a:b], None if texture_f32 is None else texture_f32[a:b])
+        if a >= lay.cells_per_row * lay.cell or 2 * (a // lay.cell) * lay.cells_per_row >= T:
+            texture[a:b].view(torch.int32).fill_(0x00FF8080)   # rows of the margin or of cells past the last triangle: what
+                                                               # encode gives an empty texel, (128, 128, 255, 0), as one word
+            if texture_f32 is not None:
+                texture_f32[a:b, :, :2] = 0
+                texture_f32[a:b, :, 2] = 1
+            continue
+        baked = ops.bake_points(vertices, triangles, A, rows=(a, b))
+        if normal_fn is not None:
+            vectors = normal_fn(baked.points.t()).to(torch.float32).t().contiguous()
+            ops.encode_normal_map(baked.texel_face, vectors, vertices, triangles, negate=False, min_length=min_gradient, out=out)
+        else:
+            points = (baked.points * cs if cs != 1 else baked.points)[None].contiguous()
+            _, gradient = ops.field_gradient(points, parts, model.canonical_pose, tri, feat_cl, pack, **flags)
+            ops.encode_normal_map(baked.texel_face, gradient[0], vertices, triangles, negate=True, min_length=min_gradient,
+                                  out=out)
+    return TextureAtlas(texture, texture_f32, T, A, lay.cell)
+
+
 @dataclasses.dataclass
 class RiggedMesh:
     """A mesh bound to the parts of the model it was extracted from: vertices (V, 3) fp32 in camera units in the rest
     pose, triangles (T, 3) int64, joints (V, K) int32 (-1: unused slot) and weights (V, K) fp32 by descending weight,
     kept_mass (V,) fp32 (the share of the part-probability mass the K kept parts carry; 0: no part contains the vertex, it
     follows the nearest), rest_pose (1, P, 4, 4) the rest part frames with UNSCALED translation, rest_bone_length
-    (1, P, 1), and optionally colors (V, 3) fp32 in [0, 1], labels (V,) int32 and texture, the TextureAtlas of the mesh
-    baked in the rest pose."""
+    (1, P, 1), and optionally colors (V, 3) fp32 in [0, 1], labels (V,) int32, texture, the TextureAtlas of the mesh
+    baked in the rest pose, and normal_map, its tangent-space normal map (bake_normal_map) in an atlas of the same layout."""
     vertices: torch.Tensor
     triangles: torch.Tensor
     joints: torch.Tensor
@@ -400,6 +448,7 @@ class RiggedMesh:
     colors: Optional[torch.Tensor] = None
     labels: Optional[torch.Tensor] = None
     texture: Optional[TextureAtlas] = None
+    normal_map: Optional[TextureAtlas] = None
 
 
 def _mask_tri_plane(model, model_input: Dict) -> torch.Tensor:
@@ -413,6 +462,29 @@ def _mask_tri_plane(model, model_input: Dict) -> torch.Tensor:
     return tri.detach()
 
 
+def _adds_normal_map_size(field_of):
+    """Decorator of a rig extractor (its result a RiggedMesh): adds the keyword `normal_map_size`, which fills the record's
+    normal_map - bake_normal_map of the final (simplified) mesh in the rest pose at that atlas size. field_of(arguments) ->
+    (model, part frames, model_input), from the extractor's bound arguments. The extractor keeps its signature: the keyword
+    belongs to the wrapper, as `return_normals` does to _adds_return_normals'."""
+    def decorate(extract):
+        signature = inspect.signature(extract)
+
+        @functools.wraps(extract)
+        def wrapper(*args, normal_map_size: Optional[int] = None, **kwargs):
+            rig = extract(*args, **kwargs)
+            if normal_map_size is None:
+                return rig
+            bound = signature.bind(*args, **kwargs)
+            bound.apply_defaults()
+            model, pose_parts, model_input = field_of(bound.arguments)
+            rig.normal_map = bake_normal_map(model, pose_parts, rig.vertices, rig.triangles, model_input, size=normal_map_size)
+            return rig
+        return wrapper
+    return decorate
+
+
+@_adds_normal_map_size(lambda a: (a["model"], a["pose_to_camera"], a["model_input"]))
 @torch.no_grad()
 def extract_rigged_mesh(model, pose_to_camera: torch.Tensor, center: torch.Tensor, voxel_size: float = 0.003,
                         mesh_th: float = 15, model_input: Dict = {}, max_influences: int = 4, return_colors: bool = False,
@@ -423,7 +495,9 @@ def extract_rigged_mesh(model, pose_to_camera: torch.Tensor, center: torch.Tenso
     the parts whose cube contains it. `return_colors` and `return_part_labels` fill the record's colors and labels as
     extract_mesh returns them; `texture_size` fills its texture: bake_texture of the mesh in this pose, in `texture_color`
     ("field" or "parts"). The mesh is posed by skin_mesh and written out by export_glb. `simplify_cell` as in extract_mesh:
-    the skin weights, colours, labels and the texture are those of the simplified mesh."""
+    the skin weights, colours, labels and the texture are those of the simplified mesh. The keyword `normal_map_size` (of
+    the decorator above) fills normal_map: the field's normals baked into an atlas of that size for the final mesh, so a
+    simplified rig keeps the shading detail of the field (paint_normal_mapped_mesh, export_glb)."""
     from ..NeRF.rendering import _parts_from_part_poses
     got = extract_mesh(model, pose_to_camera, center, voxel_size, mesh_th, model_input, return_part_labels, return_colors,
                        simplify_cell)
@@ -578,7 +652,7 @@ def _png_rgba(pixels) -> bytes:
 
 
 def export_glb(rig: RiggedMesh, path: str, texture: Optional[TextureAtlas] = None, clips: Optional[Dict] = None,
-               normals=None) -> None:
+               normals=None, normal_map: Optional[TextureAtlas] = None) -> None:
     """The rigged mesh as binary glTF 2.0 (standard library and numpy only): one mesh primitive with POSITION, optional
     COLOR_0 (float RGB), JOINTS_0 / WEIGHTS_0 and, at 8 influences, JOINTS_1 / WEIGHTS_1 (joints as unsigned bytes, an
     unused slot as joint 0 with weight 0), 32-bit indices; a flat skeleton of P joint nodes under one identity root, node
@@ -600,7 +674,15 @@ def export_glb(rig: RiggedMesh, path: str, texture: Optional[TextureAtlas] = Non
 
     `normals` (V, 3): the NORMAL attribute (float VEC3) of the rest pose, e.g. extract_mesh(return_normals=True)'s or
     field_normals at rig.vertices - de-indexed with the primitive when a texture is written; viewers skin it themselves.
-    normals=None writes the bytes a call without the keyword writes."""
+    normals=None writes the bytes a call without the keyword writes.
+
+    With a normal map (`normal_map`, else rig.normal_map: bake_normal_map's atlas of this mesh) the primitive is de-indexed
+    as with a texture - also when there is no colour texture, COLOR_0 then copied to the corners - and carries TEXCOORD_0 =
+    atlas_uv, NORMAL = the flat unit normal of each corner's triangle and TANGENT = (t^, -1) as float VEC4, t^ the tangent
+    of include/enarf_nmap.h: a viewer's bitangent cross(NORMAL, TANGENT.xyz) * w is the b^ the map was encoded in. A
+    triangle without a frame gets NORMAL (0, 0, 1) and TANGENT (1, 0, 0, -1). The material gains normalTexture, a second
+    embedded PNG that shares the sampler; without a colour texture it has no baseColorTexture. `normals=` together with a
+    normal map is a ValueError: the frame needs the face normal. Without a normal map every file is what it was."""
     import json
     import struct
     import numpy as np
@@ -643,23 +725,43 @@ def export_glb(rig: RiggedMesh, path: str, texture: Optional[TextureAtlas] = Non
 
     FLOAT, UBYTE, UINT, ARRAY, ELEMENT = 5126, 5121, 5125, 34962, 34963
     texture = rig.texture if texture is None else texture
-    if texture is not None:
-        if texture.num_triangles != len(f):
-            raise ValueError(f"export_glb: the atlas was baked for {texture.num_triangles} triangles, the mesh has {len(f)}")
-        pixels = _host(texture.texture, np.uint8)
-        if pixels.shape != (texture.size, texture.size, 4):
-            raise ValueError(f"export_glb takes a ({texture.size}, {texture.size}, 4) uint8 texture, got {pixels.shape}")
+    normal_map = getattr(rig, "normal_map", None) if normal_map is None else normal_map
+    if normal_map is not None and vn is not None:
+        raise ValueError("export_glb: normals= cannot go with a normal map: NORMAL is then the face normal the tangent frame "
+                         "is built on")
+    atlases, pixels, corner, tangent = [a for a in (texture, normal_map) if a is not None], [], None, None
+    for atlas in atlases:
+        if atlas.num_triangles != len(f):
+            raise ValueError(f"export_glb: the atlas was baked for {atlas.num_triangles} triangles, the mesh has {len(f)}")
+        pixels.append(_host(atlas.texture, np.uint8))
+        if pixels[-1].shape != (atlas.size, atlas.size, 4):
+            raise ValueError(f"export_glb takes a ({atlas.size}, {atlas.size}, 4) uint8 texture, got {pixels[-1].shape}")
+    if len(atlases) == 2 and texture.size != normal_map.size:
+        raise ValueError(f"export_glb: the texture has {texture.size} texels a side, the normal map {normal_map.size}: both "
+                         f"are read through one TEXCOORD_0")
+    if normal_map is not None:
+        from ..._nmap_lib import tangent_frames
+        t_hat, _, n_hat, _ = tangent_frames(v, f)
+        vn = np.repeat(n_hat.astype(np.float32), 3, axis=0)
+        tangent = np.repeat(np.concatenate([t_hat, np.full((len(f), 1), -1.0)], 1).astype(np.float32), 3, axis=0)
+    num_vertices = len(v)
+    if atlases:
         corner = f.reshape(-1)                             # every corner a vertex of its own: its triangle's UV
         v, joints, weights = v[corner], joints[corner], weights[corner]
-        vn = None if vn is None else vn[corner]
+        if vn is not None and normal_map is None:          # with a normal map vn is already the face normal of every corner
+            vn = vn[corner]
         f = np.arange(len(corner), dtype=np.int64).reshape(-1, 3)
     attributes = {"POSITION": add(v, "VEC3", FLOAT, ARRAY, bounds=len(v) > 0)}
     if vn is not None:
         attributes["NORMAL"] = add(vn, "VEC3", FLOAT, ARRAY)
-    if texture is not None:
-        attributes["TEXCOORD_0"] = add(atlas_uv(texture.num_triangles, texture.size).reshape(-1, 2), "VEC2", FLOAT, ARRAY)
-    elif rig.colors is not None:
+    if tangent is not None:
+        attributes["TANGENT"] = add(tangent, "VEC4", FLOAT, ARRAY)
+    if atlases:
+        attributes["TEXCOORD_0"] = add(atlas_uv(atlases[0].num_triangles, atlases[0].size).reshape(-1, 2), "VEC2", FLOAT, ARRAY)
+    if texture is None and rig.colors is not None:
         c = np.clip(np.nan_to_num(_host(rig.colors, np.float32).reshape(-1, 3), nan=0.0), 0, 1)
+        if corner is not None and len(c) == num_vertices:      # a normal map without a colour texture: colours per corner
+            c = c[corner]
         if c.shape != v.shape:
             raise ValueError(f"export_glb takes ({len(v)}, 3) colors, got {c.shape}")
         attributes["COLOR_0"] = add(c, "VEC3", FLOAT, ARRAY)
@@ -675,16 +777,22 @@ def export_glb(rig: RiggedMesh, path: str, texture: Optional[TextureAtlas] = Non
     nodes.append({"name": "mesh", "mesh": 0, "skin": 0})
     primitive = {"attributes": attributes, "indices": indices, "mode": 4}
     extra = {}
-    if texture is not None:
-        png = _png_rgba(pixels)
-        views.append({"buffer": 0, "byteOffset": sum(len(c) for c in chunks), "byteLength": len(png)})
-        chunks.append(png + b"\0" * (-len(png) % 4))
+    if atlases:
+        images = []
+        for px in pixels:                                  # the colour texture first, then the normal map
+            png = _png_rgba(px)
+            views.append({"buffer": 0, "byteOffset": sum(len(c) for c in chunks), "byteLength": len(png)})
+            chunks.append(png + b"\0" * (-len(png) % 4))
+            images.append({"bufferView": len(views) - 1, "mimeType": "image/png"})
         primitive["material"] = 0
-        extra.update(materials=[{"pbrMetallicRoughness": {"baseColorTexture": {"index": 0}, "metallicFactor": 0.0,
-                                                          "roughnessFactor": 1.0}}],
-                     textures=[{"sampler": 0, "source": 0}],
+        pbr = {"baseColorTexture": {"index": 0}} if texture is not None else {}
+        material = {"pbrMetallicRoughness": {**pbr, "metallicFactor": 0.0, "roughnessFactor": 1.0}}
+        if normal_map is not None:
+            material["normalTexture"] = {"index": len(images) - 1}
+        extra.update(materials=[material],
+                     textures=[{"sampler": 0, "source": i} for i in range(len(images))],
                      samplers=[{"magFilter": 9729, "minFilter": 9729, "wrapS": 33071, "wrapT": 33071}],
-                     images=[{"bufferView": len(views) - 1, "mimeType": "image/png"}])
+                     images=images)
     if clips:
         animations = []
         for name, (times, poses, lengths) in clips.items():
@@ -812,6 +920,33 @@ def paint_textured_mesh(vertices: torch.Tensor, triangles: torch.Tensor, atlas: 
     painted = ops.shade_textured(fragments.pix_to_face, fragments.bary,
                                  _shading_normals(fragments, vertices, triangles, normals, field), vertices, triangles,
                                  atlas.texture_f32 if use_float else atlas.texture, lit=lit)
+    return fragments, painted
+
+
+def paint_normal_mapped_mesh(vertices: torch.Tensor, triangles: torch.Tensor, normal_atlas: TextureAtlas, intrinsics,
+                             img_size: int, render_size: int = 512, atlas: Optional[TextureAtlas] = None, base_color=1.0,
+                             lit: bool = True, use_float: bool = False):
+    """The mesh drawn with its tangent-space normal map: rasterize_mesh, then ops.shade_normal_mapped on its fragment
+    buffers (libenarf_nmap.so, one launch more), with no host synchronisation. Returns (the RasterizedMesh, the namedtuple
+    (image (R, R, 3) uint8, albedo, normal, shaded (R, R, 3) fp32)). The shading normal is one bilinear tap of
+    normal_atlas.texture (of its texture_f32 with `use_float`) in the frame of the pixel's triangle, built from the
+    vertices given - the mesh may be posed (skin_mesh), the triangles are the atlases'; the albedo one tap of `atlas` (a
+    colour atlas of the same size; its texture_f32 with `use_float` when it has one) or the constant base_color. No CPU
+    fallback."""
+    for name, a in (("normal map", normal_atlas), ("colour atlas", atlas)):
+        if a is not None and a.num_triangles != triangles.shape[0]:
+            raise ValueError(f"paint_normal_mapped_mesh: the {name} was baked for {a.num_triangles} triangles, the mesh has "
+                             f"{triangles.shape[0]}")
+    if atlas is not None and atlas.size != normal_atlas.size:
+        raise ValueError(f"paint_normal_mapped_mesh: the normal map has {normal_atlas.size} texels a side, the colour atlas "
+                         f"{atlas.size}")
+    if use_float and normal_atlas.texture_f32 is None:
+        raise ValueError("paint_normal_mapped_mesh: use_float takes a normal map baked with want_float=True")
+    fragments = rasterize_mesh(vertices, triangles, intrinsics, img_size, render_size)
+    albedo = None if atlas is None else (atlas.texture_f32 if use_float and atlas.texture_f32 is not None else atlas.texture)
+    painted = ops.shade_normal_mapped(fragments.pix_to_face, fragments.bary, fragments.normals, vertices, triangles,
+                                      normal_atlas.texture_f32 if use_float else normal_atlas.texture, texture=albedo,
+                                      base_color=base_color, lit=lit)
     return fragments, painted
 
 

@@ -23,6 +23,31 @@ from ..libraries.NeRF.ray_sampler import mask_based_sampler, whole_image_grid_ra
 from .narf import TriPlaneNARF
 
 
+def _passes_on(keyword, default, callee, with_size=False):
+    """Decorator of a generator method that hands its arguments to the TriPlaneNARF method `callee`, which takes them after
+    (z_nerf, z_render) in place of z: adds `keyword` (at `default`: the method as it stands), which goes to that method
+    with the method's own arguments (and img_size = the generator's size `with_size`). The method keeps its signature."""
+    def decorate(method):
+        signature = inspect.signature(method)
+
+        @functools.wraps(method)
+        def wrapper(self, *args, **kwargs):
+            value = kwargs.pop(keyword, default)
+            if value == default:
+                return method(self, *args, **kwargs)
+            inner = {k: kwargs.pop(k) for k in list(kwargs) if k not in signature.parameters}    # an inner decorator's keywords
+            bound = signature.bind(self, *args, **kwargs)
+            bound.apply_defaults()
+            a = dict(bound.arguments)
+            a.pop("self")
+            z_nerf, z_render, _ = self._latent_parts(a.pop("z"))
+            if with_size:
+                a["img_size"] = self.size
+            return getattr(self.nerf, callee)(z=z_nerf, z_rend=z_render, **a, **inner, **{keyword: value})
+        return wrapper
+    return decorate
+
+
 class _RendererShell(nn.Module):
     """What both generators share: the config / size bookkeeping and the tri-plane NARF they wrap."""
 
@@ -233,6 +258,7 @@ class TriNARFGenerator(_RendererShell):
             frames[i] = ops.shade_fragments(f.pix_to_face, f.bary, shading, turned, triangles, lit=lit, **how).image
         return frames
 
+    @_passes_on("normal_map_size", None, "extract_rigged_mesh")
     def extract_rigged_mesh(self, pose_to_camera, z, bone_length, voxel_size=0.003, mesh_th=15, truncation_psi=0.4,
                             max_influences=4, return_colors=False, return_part_labels=False, texture_size=None,
                             texture_color="field", simplify_cell=None):
@@ -240,7 +266,9 @@ class TriNARFGenerator(_RendererShell):
         joints and weights (V, max_influences = 4 or 8) from one launch of the HIP skin-weight kernel, ready for
         render_mesh_animation, mesh_rendering.skin_mesh and mesh_rendering.export_glb; one sample, as extract_mesh.
         `texture_size` adds rig.texture, the texture atlas of the mesh baked in this pose in `texture_color` ("field" or
-        "parts"), for render_textured_mesh_animation and a textured export_glb."""
+        "parts"), for render_textured_mesh_animation and a textured export_glb. The keyword `normal_map_size` (_passes_on)
+        adds rig.normal_map, the field's normals baked into an atlas of that size for the final (simplified) mesh: the
+        animations draw it with normal_map=True, export_glb writes it as the material's normalTexture."""
         z_nerf, z_render, _ = self._latent_parts(z)
         return self.nerf.extract_rigged_mesh(pose_to_camera, z_nerf, z_render, bone_length, voxel_size, mesh_th,
                                              truncation_psi, max_influences, return_colors, return_part_labels,
@@ -254,6 +282,15 @@ class TriNARFGenerator(_RendererShell):
         z_nerf, z_render, _ = self._latent_parts(z)
         return self.nerf.bake_texture(pose_to_camera, z_nerf, z_render, bone_length, vertices, triangles, truncation_psi,
                                       size, color, palette, color_fn, want_float)
+
+    def bake_normal_map(self, pose_to_camera, z, bone_length, vertices, triangles, truncation_psi=0.4, size=1024,
+                        normal_fn=None, min_gradient=0.0, want_float=False):
+        """The tangent-space normal map of a mesh extract_mesh returned for the same arguments: a TextureAtlas
+        (mesh_rendering) of size x size texels holding the field's own normal at the surface point of every texel, in the
+        frame of the texel's triangle, from the HIP bake, gradient and encode kernels, one launch each a band of rows."""
+        z_nerf, z_render, _ = self._latent_parts(z)
+        return self.nerf.bake_normal_map(pose_to_camera, z_nerf, z_render, bone_length, vertices, triangles, truncation_psi,
+                                         size, normal_fn, min_gradient, want_float)
 
     def _passes_normals_on(render):
         """Decorator of render_textured_mesh: adds the keyword normals = "mesh" (the method as it stands) or "field", which
@@ -273,6 +310,7 @@ class TriNARFGenerator(_RendererShell):
                                                   a["texture_size"], a["color"], a["lit"], a["simplify_cell"], normals=normals)
         return wrapper
 
+    @_passes_on("normal_map", False, "render_textured_mesh", with_size=True)
     @_passes_normals_on
     def render_textured_mesh(self, pose_to_camera, intrinsics, z, bone_length, voxel_size=0.01, mesh_th=15,
                              truncation_psi=0.4, texture_size=1024, color="field", lit=True, simplify_cell=None):
@@ -288,16 +326,21 @@ class TriNARFGenerator(_RendererShell):
     del _passes_normals_on                               # a decorator, not a method
 
     def render_textured_mesh_animation(self, rig, key_poses, bone_length, intrinsics, num=100, loop=True, orbit=None,
-                                       lit=True, render_size=512, frames_per_batch=8):
+                                       lit=True, render_size=512, frames_per_batch=8, normal_map=False):
         """render_mesh_animation drawn with rig.texture (a rig from extract_rigged_mesh(texture_size=...)): (frames
         (num, R, R, 3) uint8, poses (num, J, 4, 4) in key_poses' dtype), device tensors, with no host synchronisation
         inside. One interpolate_pose launch; the frames posed frames_per_batch at a time by one skin_pose launch; every
         frame one rasterize_mesh and one shade_textured: the texture was baked once, in the rest pose, and moves with the
-        triangles. The bytes do not depend on frames_per_batch."""
+        triangles. The bytes do not depend on frames_per_batch. normal_map=True shades every frame with rig.normal_map (a
+        rig from extract_rigged_mesh(normal_map_size=...), the same atlas size as the texture) in place of the face normals:
+        one shade_normal_mapped launch a frame instead of the shade_textured one, the map baked once in the rest pose, its
+        frame rebuilt from the posed vertices."""
         from .. import ops
         from ..libraries.NARF.mesh_rendering import rasterize_mesh, skin_mesh
         if rig.texture is None:
             raise ValueError("render_textured_mesh_animation takes a rig extracted with texture_size=...")
+        if normal_map:
+            self._check_normal_map("render_textured_mesh_animation", rig, rig.texture.size)
         if rig.texture.num_triangles != rig.triangles.shape[0]:
             raise ValueError(f"render_textured_mesh_animation: the atlas was baked for {rig.texture.num_triangles} triangles, "
                              f"the rig has {rig.triangles.shape[0]}")
@@ -318,24 +361,46 @@ class TriNARFGenerator(_RendererShell):
                 skin_mesh(nerf, rig, pose_parts, bl, out=posed[:b - a])
                 for i in range(a, b):
                     f = rasterize_mesh(posed[i - a], rig.triangles, intrinsics, self.size, R)
-                    frames[i] = ops.shade_textured(f.pix_to_face, f.bary, f.normals, posed[i - a], rig.triangles,
-                                                   rig.texture.texture, lit=lit).image
+                    if normal_map:
+                        frames[i] = ops.shade_normal_mapped(f.pix_to_face, f.bary, f.normals, posed[i - a], rig.triangles,
+                                                            rig.normal_map.texture, texture=rig.texture.texture, lit=lit).image
+                    else:
+                        frames[i] = ops.shade_textured(f.pix_to_face, f.bary, f.normals, posed[i - a], rig.triangles,
+                                                       rig.texture.texture, lit=lit).image
         return frames, poses
 
+    @staticmethod
+    def _check_normal_map(who, rig, size=None):
+        """ValueError unless rig.normal_map is a normal map of the rig's triangles (and of `size` texels a side)"""
+        if getattr(rig, "normal_map", None) is None:
+            raise ValueError(f"{who}: normal_map=True takes a rig extracted with normal_map_size=...")
+        if rig.normal_map.num_triangles != rig.triangles.shape[0]:
+            raise ValueError(f"{who}: the normal map was baked for {rig.normal_map.num_triangles} triangles, the rig has "
+                             f"{rig.triangles.shape[0]}")
+        if size is not None and rig.normal_map.size != size:
+            raise ValueError(f"{who}: the normal map has {rig.normal_map.size} texels a side, the texture {size}: bake both at "
+                             f"one size")
+
     def render_mesh_animation(self, rig, key_poses, bone_length, intrinsics, num=100, loop=True, orbit=None, color="field",
-                              lit=True, render_size=512, frames_per_batch=8):
+                              lit=True, render_size=512, frames_per_batch=8, normal_map=False, base_color=1.0):
         """The rigged mesh in motion, without a new extraction: (frames (num, R, R, 3) uint8, poses (num, J, 4, 4) in
         key_poses' dtype), device tensors, with no host synchronisation inside. One interpolate_pose launch; the frames
         posed frames_per_batch at a time by one skin_pose launch (linear-blend skinning of `rig`, the RiggedMesh of
         extract_rigged_mesh); every frame one rasterize_mesh and one shade_fragments, as render_mesh_turntable.
         color="field" draws rig.colors, "parts" the palette colours of rig.labels, None the white mesh; bone_length
         (1, J - 1, 1) are the bone lengths of the animation (a bone longer than the rig's stretches its part). The bytes
-        do not depend on frames_per_batch."""
+        do not depend on frames_per_batch. normal_map=True with color=None draws the mesh in the constant base_color shaded
+        with rig.normal_map (extract_rigged_mesh(normal_map_size=...)): one shade_normal_mapped launch a frame."""
         from .. import ops
         from ..libraries.NARF.mesh_rendering import rasterize_mesh, skin_mesh
         from ..libraries.NeRF.rendering import semantic_palette
         if color not in ("field", "parts", None):
             raise ValueError(f"color is 'field', 'parts' or None (the white mesh), got {color!r}")
+        if normal_map:
+            if color is not None:
+                raise ValueError("render_mesh_animation: normal_map=True draws a constant base_color (color=None); a coloured "
+                                 "normal-mapped rig is render_textured_mesh_animation's")
+            self._check_normal_map("render_mesh_animation", rig)
         if color == "field" and rig.colors is None or color == "parts" and rig.labels is None:
             raise ValueError(f"color={color!r} takes a rig extracted with "
                              f"{'return_colors' if color == 'field' else 'return_part_labels'}=True")
@@ -361,6 +426,10 @@ class TriNARFGenerator(_RendererShell):
                 skin_mesh(nerf, rig, pose_parts, bl, out=posed[:b - a])
                 for i in range(a, b):
                     f = rasterize_mesh(posed[i - a], rig.triangles, intrinsics, self.size, R)
+                    if normal_map:
+                        frames[i] = ops.shade_normal_mapped(f.pix_to_face, f.bary, f.normals, posed[i - a], rig.triangles,
+                                                            rig.normal_map.texture, base_color=base_color, lit=lit).image
+                        continue
                     frames[i] = (ops.shade_fragments(f.pix_to_face, f.bary, f.normals, posed[i - a], rig.triangles, lit=lit,
                                                      **how).image if how else f.image)
         return frames, poses

@@ -25,7 +25,7 @@ import torch
 from torch import nn
 
 from .. import ops
-from ..libraries.NARF.mesh_rendering import _adds_return_normals
+from ..libraries.NARF.mesh_rendering import _adds_normal_map_size, _adds_return_normals
 from ..libraries.NARF.pose_utils import transform_pose
 from ..libraries.NeRF.utils import multi_part_positional_encoding
 from ..libraries.NeRF.rendering import _parts_from_part_poses, render, render_entire_img
@@ -414,13 +414,17 @@ class TriPlaneNARF(nn.Module):
         return extract_mesh(self, pose_parts, center, voxel_size, mesh_th, model_input, return_part_labels, return_colors,
                             simplify_cell)
 
+    @_adds_normal_map_size(lambda a: a["self"].mesh_field(a["pose_to_camera"], a["z"], a["z_rend"], a["bone_length"],
+                                                          a["truncation_psi"]))
     def extract_rigged_mesh(self, pose_to_camera, z, z_rend, bone_length, voxel_size=0.003, mesh_th=15, truncation_psi=0.4,
                             max_influences=4, return_colors=False, return_part_labels=False, texture_size=None,
                             texture_color="field", simplify_cell=None):
         """extract_mesh (with its `simplify_cell`) in the rest pose pose_to_camera (1, J, 4, 4), bound to the parts: the RiggedMesh of
         mesh_rendering.extract_rigged_mesh (vertices, triangles, joints and weights (V, max_influences), kept_mass, the
         rest part frames and bone lengths, optional colours and labels). One skin-weight launch more than extract_mesh;
-        `texture_size` adds the texture atlas of the mesh, baked in this pose in `texture_color`."""
+        `texture_size` adds the texture atlas of the mesh, baked in this pose in `texture_color`. The keyword
+        `normal_map_size` (mesh_rendering._adds_normal_map_size) adds rig.normal_map, the field's normals baked into an
+        atlas of that size for the final (simplified) mesh."""
         from ..libraries.NARF.mesh_rendering import extract_rigged_mesh
         center, pose_parts, model_input = self._mesh_inputs(pose_to_camera, z, z_rend, bone_length, truncation_psi)
         return extract_rigged_mesh(self, pose_parts, center, voxel_size, mesh_th, model_input, max_influences, return_colors,
@@ -434,6 +438,15 @@ class TriPlaneNARF(nn.Module):
         from ..libraries.NARF.mesh_rendering import bake_texture
         _, pose_parts, model_input = self._mesh_inputs(pose_to_camera, z, z_rend, bone_length, truncation_psi)
         return bake_texture(self, pose_parts, vertices, triangles, model_input, size, color, palette, color_fn, want_float)
+
+    def bake_normal_map(self, pose_to_camera, z, z_rend, bone_length, vertices, triangles, truncation_psi=0.4, size=1024,
+                        normal_fn=None, min_gradient=0.0, want_float=False):
+        """The tangent-space normal map of a mesh extracted in the pose pose_to_camera (1, J, 4, 4): the TextureAtlas of
+        mesh_rendering.bake_normal_map, size x size texels, every texel a triangle owns holding the field's normal
+        (-grad density, normalised) at the texel's surface point in the frame of its triangle; one sample."""
+        from ..libraries.NARF.mesh_rendering import bake_normal_map
+        _, pose_parts, model_input = self._mesh_inputs(pose_to_camera, z, z_rend, bone_length, truncation_psi)
+        return bake_normal_map(self, pose_parts, vertices, triangles, model_input, size, normal_fn, min_gradient, want_float)
 
     def _textured_mesh(self, pose_to_camera, z, z_rend, bone_length, voxel_size, mesh_th, truncation_psi, texture_size, color,
                        simplify_cell):
@@ -469,6 +482,33 @@ class TriPlaneNARF(nn.Module):
             return painted.image.cpu().numpy(), (vertices, triangles, atlas)
         return wrapper
 
+    def _adds_normal_map(render):
+        """Decorator of render_textured_mesh: adds the keyword normal_map = False (the method as it stands) or True: the
+        field's normals are baked into a second atlas of texture_size (bake_normal_map) and the mesh is shaded with it
+        (paint_normal_mapped_mesh, the texture as the albedo); the result then ends with that atlas: (image, (vertices,
+        triangles, the TextureAtlas, the normal map)). The method keeps its signature."""
+        signature = inspect.signature(render)
+
+        @functools.wraps(render)
+        def wrapper(self, *args, normal_map=False, **kwargs):
+            if not normal_map:
+                return render(self, *args, **kwargs)
+            from ..libraries.NARF.mesh_rendering import bake_normal_map, paint_normal_mapped_mesh
+            if kwargs.pop("normals", "mesh") != "mesh":
+                raise ValueError("render_textured_mesh: normal_map=True and normals='field' are two sources of one normal")
+            bound = signature.bind(self, *args, **kwargs)
+            bound.apply_defaults()
+            a = bound.arguments
+            vertices, triangles, atlas, (_, pose_parts, model_input) = self._textured_mesh(
+                a["pose_to_camera"], a["z"], a["z_rend"], a["bone_length"], a["voxel_size"], a["mesh_th"], a["truncation_psi"],
+                a["texture_size"], a["color"], a["simplify_cell"])
+            normal_atlas = bake_normal_map(self, pose_parts, vertices, triangles, model_input, a["texture_size"])
+            _, painted = paint_normal_mapped_mesh(vertices, triangles, normal_atlas, a["intrinsics"], a["img_size"],
+                                                  atlas=atlas, lit=a["lit"])
+            return painted.image.cpu().numpy(), (vertices, triangles, atlas, normal_atlas)
+        return wrapper
+
+    @_adds_normal_map
     @_adds_field_shading
     def render_textured_mesh(self, pose_to_camera, intrinsics, z, z_rend, bone_length, voxel_size=0.01, mesh_th=15,
                              truncation_psi=0.4, img_size=128, texture_size=1024, color="field", lit=True,
@@ -485,7 +525,7 @@ class TriPlaneNARF(nn.Module):
         _, painted = paint_textured_mesh(vertices, triangles, atlas, intrinsics, img_size, lit=lit)
         return painted.image.cpu().numpy(), (vertices, triangles, atlas)
 
-    del _adds_field_shading                              # a decorator, not a method
+    del _adds_field_shading, _adds_normal_map            # decorators, not methods
 
     def part_labels(self, points, pose_to_camera, z, bone_length, truncation_psi=1, points_last=False,
                     return_valid_bits=False):

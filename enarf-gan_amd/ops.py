@@ -992,6 +992,37 @@ def shade_textured(pix_to_face: torch.Tensor, bary: torch.Tensor, normals: torch
     return _bake_lib.shade_textured(pix_to_face, bary, normals, vertices, triangles, texture, lit, background)
 
 
+# ------------------------------------------------------------------------------------------------- normal-mapped meshes
+from ._nmap_lib import NormalMappedFragments, NormalMapTexture  # noqa: E402,F401  (the results of the two ops below)
+
+
+def encode_normal_map(texel_face: torch.Tensor, vectors: torch.Tensor, vertices: torch.Tensor, triangles: torch.Tensor,
+                      negate: bool = True, min_length: float = 0.0, want_float: bool = False, out=None):
+    """The vectors found at bake_points' points to a tangent-space normal map, in one launch of libenarf_nmap.so: the
+    namedtuple (texture (rows, A, 4) uint8, texture_f32 (rows, A, 3) fp32 or None). texel_face (rows, A) int32 as
+    bake_points returns it, vectors (3, rows A) fp32 as three planes (what field_gradient returns per image), the mesh the
+    atlas belongs to. The normal of a texel is -vector with `negate` (a density gradient), else vector, expressed in the
+    frame (t^, b^, n^) of the texel's triangle (include/enarf_nmap.h) and stored as round(255 (c + 1) / 2); a texel whose
+    vector is no longer than min_length or not finite, or whose triangle has no frame, is the flat (128, 128, 255); an
+    empty texel the same with alpha 0. `out` as in bake_resolve. ValueError for shapes, dtypes and devices before a device
+    is touched; no CPU fallback."""
+    from . import _nmap_lib
+    return _nmap_lib.encode_normal_map(texel_face, vectors, vertices, triangles, negate, min_length, want_float, out)
+
+
+def shade_normal_mapped(pix_to_face: torch.Tensor, bary: torch.Tensor, normals: torch.Tensor, vertices: torch.Tensor,
+                        triangles: torch.Tensor, normal_texture: torch.Tensor, texture: Optional[torch.Tensor] = None,
+                        base_color=1.0, lit: bool = True, background=1.0):
+    """shade_textured with the shading normal read from a tangent-space normal map, in one launch of libenarf_nmap.so: the
+    namedtuple (image (R, R, 3) uint8, albedo, normal, shaded (R, R, 3) fp32). normal_texture (A, A, 4) uint8 or (A, A, 3)
+    fp32 as encode_normal_map wrote it; the albedo is one tap of `texture` (either kind of shade_textured, the same A) or
+    the constant base_color. The frame is rebuilt per pixel from the vertices given here, so a posed mesh (skin_mesh)
+    carries its map along. Bit-identical from run to run, nothing synchronises, no CPU fallback."""
+    from . import _nmap_lib
+    return _nmap_lib.shade_normal_mapped(pix_to_face, bary, normals, vertices, triangles, normal_texture, texture, base_color,
+                                         lit, background)
+
+
 # ------------------------------------------------------------------------------------------------- simplified meshes
 def simplify_mesh(vertices: torch.Tensor, triangles: torch.Tensor, cell: float, origin=None, placement: str = "quadric",
                   reg: float = 1e-3):

@@ -32,7 +32,10 @@ bakes the field's colour into an N x N texture atlas of that mesh (libenarf_bake
 place of the vertex colours, and `--skinned-mesh texture` draws the posed mesh with it; `--clip` writes the interpolated
 sequence into the glTF as an animation clip. `--simplify CELL` simplifies the extracted mesh of --skinned-mesh,
 --mesh-turntable and --export-glb to cells of CELL (libenarf_simp.so: vertex clustering with quadric placement) before it is
-coloured, rigged and baked: extract at a fine --voxel-size, keep few triangles."""
+coloured, rigged and baked: extract at a fine --voxel-size, keep few triangles. `--normal-map-size N` bakes the field's
+own normals into an N x N tangent-space normal map of that (simplified) mesh (libenarf_nmap.so): `--skinned-mesh texture`
+(N must then be the texture's size) and `--skinned-mesh white` shade the posed mesh with it, and --export-glb writes it as
+the material's normalTexture, with tangents."""
 import argparse
 import math
 import os
@@ -82,6 +85,9 @@ def main():
     ap.add_argument("--simplify", type=float, default=None, metavar="CELL",
                     help="simplify the extracted mesh to cells of this size (the poses' units) before colouring, rigging "
                          "and baking it")
+    ap.add_argument("--normal-map-size", type=int, default=None, metavar="N",
+                    help="bake the field's normals into a tangent-space normal map of this size: --skinned-mesh texture|white "
+                         "shade with it, --export-glb embeds it")
     ap.add_argument("--voxel-size", type=float, default=0.003, help="mesh turntable: the density sweep's voxel")
     ap.add_argument("--mesh-th", type=float, default=15.0, help="mesh turntable: the density threshold")
     ap.add_argument("--unlit", action="store_true", help="mesh turntable: the colour itself, without the Phong terms")
@@ -117,12 +123,14 @@ def main():
         orbit = torch.arange(args.num, dtype=torch.float64, device=dev) * (2 * math.pi * args.orbit_turns / args.num)
     rig = None
     textured = args.skinned_mesh == "texture"
+    if args.normal_map_size is not None and args.skinned_mesh in ("field", "parts"):
+        raise SystemExit("--normal-map-size shades --skinned-mesh texture or white (the vertex colours have no normal-mapped shade)")
     if args.skinned_mesh or args.export_glb:
         rig = gen.extract_rigged_mesh(key_poses[:1].float(), z, bone_length, voxel_size=args.voxel_size, mesh_th=args.mesh_th,
                                       truncation_psi=args.truncation_psi, max_influences=args.influences,
                                       return_colors=True, return_part_labels=True,
                                       texture_size=1024 if textured and args.texture_size is None else args.texture_size,
-                                      simplify_cell=args.simplify)
+                                      simplify_cell=args.simplify, normal_map_size=args.normal_map_size)
         if args.export_glb:
             from enarf_gan_amd import ops
             from enarf_gan_amd.libraries.NARF.mesh_rendering import export_glb
@@ -135,16 +143,19 @@ def main():
             print(f"{args.export_glb}: {len(rig.vertices)} vertices, {len(rig.triangles)} triangles, "
                   f"{rig.joints.shape[1]} influences"
                   + (f", a {rig.texture.size} x {rig.texture.size} texture (cell {rig.texture.cell})" if rig.texture else "")
+                  + (f", a {rig.normal_map.size} x {rig.normal_map.size} normal map" if rig.normal_map else "")
                   + (f", a clip of {len(clips['sequence'][0])} keys" if clips else ""), file=sys.stderr)
     if textured:
         frames, _ = gen.render_textured_mesh_animation(rig, key_poses, bone_length, intrinsics, num=args.num,
                                                        loop=not args.no_loop, orbit=orbit, lit=not args.unlit,
-                                                       render_size=args.render_size, frames_per_batch=args.frames_per_batch)
+                                                       render_size=args.render_size, frames_per_batch=args.frames_per_batch,
+                                                       normal_map=args.normal_map_size is not None)
     elif args.skinned_mesh:
         frames, _ = gen.render_mesh_animation(rig, key_poses, bone_length, intrinsics, num=args.num, loop=not args.no_loop,
                                               orbit=orbit, color=None if args.skinned_mesh == "white" else args.skinned_mesh,
                                               lit=not args.unlit, render_size=args.render_size,
-                                              frames_per_batch=args.frames_per_batch)
+                                              frames_per_batch=args.frames_per_batch,
+                                              normal_map=args.normal_map_size is not None)
     elif args.mesh_turntable:
         angles = torch.arange(args.num, dtype=torch.float32, device=dev) * (2 * math.pi / args.num)
         frames = gen.render_mesh_turntable(key_poses[:1].float(), intrinsics, z, bone_length, angles,

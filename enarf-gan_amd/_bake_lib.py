@@ -2,8 +2,8 @@
 the surface point of every texel, the RGBA8 texture from the colours or labels found there, and the deferred textured
 shading of the fragment buffers rasterize_mesh returns - on the device.
 
-Loading, return codes and the device-argument checks are `_loader`'s. `bake_layout` and `atlas_corners` restate the atlas
-layout on the host and need neither the library nor a device.
+Loading, return codes and the argument checks more than one binding makes are `_loader`'s. `bake_layout` and
+`atlas_corners` restate the atlas layout on the host and need neither the library nor a device.
 """
 from __future__ import annotations
 
@@ -11,7 +11,7 @@ import ctypes as C
 from collections import namedtuple
 from typing import Tuple
 
-from ._loader import Library, stream_of
+from ._loader import Library, check_tensors, fragment_size, mesh_shapes, on_device, rgb, stream_of, texture_kind
 from ._paint_lib import ShadedFragments
 
 ABI_VERSION = 1
@@ -96,56 +96,11 @@ def atlas_corners(T: int, size: int):
     return (origin[:, None, :] + local[h]).astype(np.float64)
 
 
-def _rgb(value, who: str, name: str) -> Tuple[float, float, float]:
-    """a number or three numbers -> three floats, or ValueError"""
-    try:
-        v = [float(value)] * 3 if not hasattr(value, "__len__") else [float(x) for x in value]
-    except (TypeError, ValueError):
-        raise ValueError(f"{who} takes a number or three numbers as {name}, got {value!r}") from None
-    if len(v) != 3:
-        raise ValueError(f"{who} takes a number or three numbers as {name}, got {len(v)} values")
-    return v[0], v[1], v[2]
-
-
-def _tensors(who: str, want: dict, **named) -> None:
-    import torch
-    for name, t in named.items():
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"{who} takes tensors; {name} is {type(t).__name__}")
-        if t.dtype != want.get(name, torch.float32):
-            raise ValueError(f"{who} takes {want.get(name, torch.float32)} {name}, got {t.dtype}")
-
-
-def _on_device(who: str, **named):
-    """the one device of the tensors, or ValueError"""
-    dev = None
-    for name, t in named.items():
-        if t is None:
-            continue
-        if t.device.type != "cuda":
-            raise ValueError(f"{who} takes device tensors (there is no CPU fallback); {name} is on {t.device}")
-        if dev is not None and t.device != dev:
-            raise ValueError(f"{who}: {name} is on {t.device}, other arguments on {dev}")
-        dev = t.device
-    return dev
-
-
-def _mesh_shapes(who: str, vertices, triangles) -> Tuple[int, int]:
-    if vertices.dim() != 2 or vertices.shape[1] != 3:
-        raise ValueError(f"{who} takes (V, 3) vertices, got {tuple(vertices.shape)}")
-    if triangles.dim() != 2 or triangles.shape[1] != 3:
-        raise ValueError(f"{who} takes (T, 3) triangles, got {tuple(triangles.shape)}")
-    V, T = vertices.shape[0], triangles.shape[0]
-    if V >= 2 ** 31 or T >= 2 ** 31:
-        raise ValueError(f"{who}: V = {V}, T = {T}: both must lie in [0, 2^31)")
-    return V, T
-
-
 def check_points_args(vertices, triangles, size, rows) -> Tuple[int, int, int, int, int]:
     """(V, T, A, row0, rows) of a bake_points call, or ValueError / NotImplementedError; touches no device"""
     import torch
-    _tensors("bake_points", dict(triangles=torch.int64), vertices=vertices, triangles=triangles)
-    V, T = _mesh_shapes("bake_points", vertices, triangles)
+    check_tensors("bake_points", dict(triangles=torch.int64), vertices=vertices, triangles=triangles)
+    V, T = mesh_shapes("bake_points", vertices, triangles)
     bake_layout(T, size)
     A = int(size)
     if rows is None:
@@ -166,7 +121,7 @@ def bake_points(vertices, triangles, size: int, rows=None) -> BakedPoints:
     default), on the mesh's device and its current stream, one launch, no synchronisation."""
     import torch
     V, T, A, row0, count = check_points_args(vertices, triangles, size, rows)
-    dev = _on_device("bake_points", vertices=vertices, triangles=triangles)
+    dev = on_device("bake_points", vertices=vertices, triangles=triangles)
     lib = load()
     keep = [vertices.contiguous(), triangles.contiguous()]
     with torch.cuda.device(dev):
@@ -195,7 +150,7 @@ def check_resolve_args(texel_face, color, labels, palette, out) -> Tuple[tuple, 
         if palette is None:
             raise ValueError("bake_resolve: labels need a (P, 3) palette")
         named.update(labels=labels, palette=palette)
-    _tensors("bake_resolve", dict(texel_face=torch.int32, labels=torch.int32), **named)
+    check_tensors("bake_resolve", dict(texel_face=torch.int32, labels=torch.int32), **named)
     shape = tuple(texel_face.shape)
     M = texel_face.numel()
     if len(shape) != 2 or not 1 <= M <= MAX_ATLAS * MAX_ATLAS:
@@ -227,9 +182,9 @@ def bake_resolve(texel_face, color=None, labels=None, palette=None, fill=0.0, ne
     (rows of a whole atlas, say)."""
     import torch
     shape, M, P = check_resolve_args(texel_face, color, labels, palette, out)
-    fl, nt = _rgb(fill, "bake_resolve", "fill"), _rgb(neutral, "bake_resolve", "neutral")
-    dev = _on_device("bake_resolve", texel_face=texel_face, color=color, labels=labels, palette=palette,
-                     texture=None if out is None else out[0], texture_f32=None if out is None else out[1])
+    fl, nt = rgb(fill, "bake_resolve", "fill"), rgb(neutral, "bake_resolve", "neutral")
+    dev = on_device("bake_resolve", texel_face=texel_face, color=color, labels=labels, palette=palette,
+                    texture=None if out is None else out[0], texture_f32=None if out is None else out[1])
     lib = load()
     keep = [None if t is None else t.contiguous() for t in (texel_face, color, labels, palette)]
     with torch.cuda.device(dev):
@@ -252,28 +207,13 @@ def bake_resolve(texel_face, color=None, labels=None, palette=None, fill=0.0, ne
 def check_shade_args(pix_to_face, bary, normals, vertices, triangles, texture) -> Tuple[int, int, int, int, bool]:
     """(R, V, T, A, the texture is fp32) of a shade_textured call, or ValueError / NotImplementedError; touches no device"""
     import torch
-    _tensors("shade_textured", dict(pix_to_face=torch.int64, triangles=torch.int64), pix_to_face=pix_to_face, bary=bary,
-             normals=normals, vertices=vertices, triangles=triangles)
-    if not isinstance(texture, torch.Tensor):
-        raise ValueError(f"shade_textured takes tensors; texture is {type(texture).__name__}")
-    if texture.dtype not in (torch.uint8, torch.float32):
-        raise ValueError(f"shade_textured takes a uint8 (A, A, 4) or an fp32 (A, A, 3) texture, got {texture.dtype}")
-    is_f32 = texture.dtype == torch.float32
-    ts = tuple(texture.shape)
-    if len(ts) != 3 or ts[0] != ts[1] or ts[2] != (3 if is_f32 else 4):
-        raise ValueError(f"shade_textured takes a uint8 (A, A, 4) or an fp32 (A, A, 3) texture, got {texture.dtype} {ts}")
-    shape = tuple(pix_to_face.shape)
-    if len(shape) != 2 or shape[0] != shape[1]:
-        raise ValueError(f"shade_textured takes (R, R) pix_to_face, got {shape}")
-    R = shape[0]
-    if not 1 <= R <= MAX_SIZE:
-        raise ValueError(f"shade_textured: render size {R} outside [1, {MAX_SIZE}]")
-    for name, t in (("bary", bary), ("normals", normals)):
-        if tuple(t.shape) != (R, R, 3):
-            raise ValueError(f"shade_textured takes ({R}, {R}, 3) {name}, got {tuple(t.shape)}")
-    V, T = _mesh_shapes("shade_textured", vertices, triangles)
-    bake_layout(T, ts[0])
-    return R, V, T, ts[0], is_f32
+    check_tensors("shade_textured", dict(pix_to_face=torch.int64, triangles=torch.int64), pix_to_face=pix_to_face, bary=bary,
+                  normals=normals, vertices=vertices, triangles=triangles)
+    A, is_f32 = texture_kind("shade_textured", "texture", texture)
+    R = fragment_size("shade_textured", MAX_SIZE, pix_to_face, bary, normals)
+    V, T = mesh_shapes("shade_textured", vertices, triangles)
+    bake_layout(T, A)
+    return R, V, T, A, is_f32
 
 
 def shade_textured(pix_to_face, bary, normals, vertices, triangles, texture, lit: bool = True, background=1.0
@@ -282,9 +222,9 @@ def shade_textured(pix_to_face, bary, normals, vertices, triangles, texture, lit
     current stream, one launch, no synchronisation; the contract is in include/enarf_bake.h."""
     import torch
     R, V, T, A, is_f32 = check_shade_args(pix_to_face, bary, normals, vertices, triangles, texture)
-    bg = _rgb(background, "shade_textured", "background")
-    dev = _on_device("shade_textured", pix_to_face=pix_to_face, bary=bary, normals=normals, vertices=vertices,
-                     triangles=triangles, texture=texture)
+    bg = rgb(background, "shade_textured", "background")
+    dev = on_device("shade_textured", pix_to_face=pix_to_face, bary=bary, normals=normals, vertices=vertices,
+                    triangles=triangles, texture=texture)
     lib = load()
     keep = [t.contiguous() for t in (pix_to_face, bary, normals, vertices, triangles, texture)]
     ptr = lambda t: t.data_ptr() if t.numel() else None

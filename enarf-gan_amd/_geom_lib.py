@@ -10,7 +10,7 @@ import ctypes as C
 from collections import namedtuple
 from typing import Tuple
 
-from ._loader import Library, device_of, stream_of
+from ._loader import Library, device_of, rgb, stream_of
 
 ABI_VERSION = 1
 
@@ -48,17 +48,6 @@ GeometryBuffers = namedtuple("GeometryBuffers", OUTPUTS)
 
 _library = Library("geom", ABI_VERSION, SIGNATURES, "The geometry kernels have no CPU fallback.")
 load, check = _library.load, _library.check
-
-
-def _rgb(value, name: str) -> Tuple[float, float, float]:
-    """a number or three numbers -> three floats, or ValueError"""
-    try:
-        v = [float(value)] * 3 if not hasattr(value, "__len__") else [float(x) for x in value]
-    except (TypeError, ValueError):
-        raise ValueError(f"geometry_buffers takes a number or three numbers as {name}, got {value!r}") from None
-    if len(v) != 3:
-        raise ValueError(f"geometry_buffers takes a number or three numbers as {name}, got {len(v)} values")
-    return v[0], v[1], v[2]
 
 
 def _number(value, name: str) -> float:
@@ -131,7 +120,7 @@ def geometry_buffers(disparity, mask, inv_intrinsics, size=None, origin=(0, 0), 
     import torch
     B, H, W, KB = check_buffers_args(disparity, mask, inv_intrinsics, size, origin, step, shade, near, far, want)
     want = tuple(want)
-    bg = _rgb(background, "background")
+    bg = rgb(background, "geometry_buffers", "background")
     scalars = {n: _number(v, n) for n, v in dict(x0=origin[0], y0=origin[1], step=step, depth_scale=depth_scale,
                                                  mask_threshold=mask_threshold, edge=edge).items()}
     shapes = dict(depth=((B, H, W), torch.float32), points=((B, H, W, 3), torch.float32),

@@ -2,7 +2,7 @@
 atlas of an extracted mesh - a vector per texel encoded in the frame of the texel's triangle, and the deferred shading of
 the fragment buffers rasterize_mesh returns with such a map - on the device.
 
-Loading, return codes and the device-argument checks are `_loader`'s; the atlas layout and the small argument helpers are
+Loading, return codes and the argument checks more than one binding makes are `_loader`'s; the atlas layout is
 `_bake_lib`'s. `tangent_frames` restates the frame on the host and needs neither the library nor a device.
 """
 from __future__ import annotations
@@ -11,8 +11,8 @@ import ctypes as C
 from collections import namedtuple
 from typing import Tuple
 
-from ._bake_lib import MAX_ATLAS, MAX_SIZE, _mesh_shapes, _on_device, _rgb, _tensors, bake_layout
-from ._loader import Library, stream_of
+from ._bake_lib import MAX_ATLAS, MAX_SIZE, bake_layout
+from ._loader import Library, check_tensors, fragment_size, mesh_shapes, on_device, rgb, stream_of, texture_kind
 
 ABI_VERSION = 1
 
@@ -70,15 +70,15 @@ def tangent_frames(vertices, triangles):
 def check_encode_args(texel_face, vectors, vertices, triangles, min_length, out) -> Tuple[tuple, int, int, int, float]:
     """(the shape of texel_face, count, V, T, min_length) of an encode_normal_map call, or ValueError; touches no device"""
     import torch
-    _tensors("encode_normal_map", dict(texel_face=torch.int32, triangles=torch.int64), texel_face=texel_face, vectors=vectors,
-             vertices=vertices, triangles=triangles)
+    check_tensors("encode_normal_map", dict(texel_face=torch.int32, triangles=torch.int64), texel_face=texel_face,
+                  vectors=vectors, vertices=vertices, triangles=triangles)
     shape = tuple(texel_face.shape)
     M = texel_face.numel()
     if len(shape) != 2 or M > MAX_ATLAS * MAX_ATLAS:
         raise ValueError(f"encode_normal_map takes (rows, A) texel_face of at most {MAX_ATLAS}^2 texels, got {shape}")
     if tuple(vectors.shape) != (3, M):
         raise ValueError(f"encode_normal_map takes (3, {M}) vectors (three planes), got {tuple(vectors.shape)}")
-    V, T = _mesh_shapes("encode_normal_map", vertices, triangles)
+    V, T = mesh_shapes("encode_normal_map", vertices, triangles)
     try:
         ml = float(min_length)
     except (TypeError, ValueError):
@@ -105,8 +105,8 @@ def encode_normal_map(texel_face, vectors, vertices, triangles, negate: bool = T
     tensors (rows of a whole atlas, say)."""
     import torch
     shape, M, V, T, ml = check_encode_args(texel_face, vectors, vertices, triangles, min_length, out)
-    dev = _on_device("encode_normal_map", texel_face=texel_face, vectors=vectors, vertices=vertices, triangles=triangles,
-                     texture=None if out is None else out[0], texture_f32=None if out is None else out[1])
+    dev = on_device("encode_normal_map", texel_face=texel_face, vectors=vectors, vertices=vertices, triangles=triangles,
+                    texture=None if out is None else out[0], texture_f32=None if out is None else out[1])
     lib = load()
     keep = [t.contiguous() for t in (texel_face, vectors, vertices, triangles)]
     ptr = lambda t: t.data_ptr() if t.numel() else None
@@ -126,43 +126,21 @@ def encode_normal_map(texel_face, vectors, vertices, triangles, negate: bool = T
     return res
 
 
-def _texture_kind(who: str, name: str, texture) -> Tuple[int, bool]:
-    """(A, the texture is fp32) of a uint8 (A, A, 4) or an fp32 (A, A, 3) texture, or ValueError"""
-    import torch
-    if not isinstance(texture, torch.Tensor):
-        raise ValueError(f"{who} takes tensors; {name} is {type(texture).__name__}")
-    if texture.dtype not in (torch.uint8, torch.float32):
-        raise ValueError(f"{who} takes a uint8 (A, A, 4) or an fp32 (A, A, 3) {name}, got {texture.dtype}")
-    is_f32 = texture.dtype == torch.float32
-    ts = tuple(texture.shape)
-    if len(ts) != 3 or ts[0] != ts[1] or ts[2] != (3 if is_f32 else 4):
-        raise ValueError(f"{who} takes a uint8 (A, A, 4) or an fp32 (A, A, 3) {name}, got {texture.dtype} {ts}")
-    return ts[0], is_f32
-
-
 def check_shade_args(pix_to_face, bary, normals, vertices, triangles, normal_texture, texture):
     """(R, V, T, A, the normal texture is fp32, the albedo texture is fp32 or None without one) of a shade_normal_mapped
     call, or ValueError / NotImplementedError; touches no device"""
     import torch
     who = "shade_normal_mapped"
-    _tensors(who, dict(pix_to_face=torch.int64, triangles=torch.int64), pix_to_face=pix_to_face, bary=bary,
-             normals=normals, vertices=vertices, triangles=triangles)
-    A, n_f32 = _texture_kind(who, "normal_texture", normal_texture)
+    check_tensors(who, dict(pix_to_face=torch.int64, triangles=torch.int64), pix_to_face=pix_to_face, bary=bary,
+                  normals=normals, vertices=vertices, triangles=triangles)
+    A, n_f32 = texture_kind(who, "normal_texture", normal_texture)
     t_f32 = None
     if texture is not None:
-        At, t_f32 = _texture_kind(who, "texture", texture)
+        At, t_f32 = texture_kind(who, "texture", texture)
         if At != A:
             raise ValueError(f"{who}: the normal texture has {A} texels a side, the albedo texture {At}: one atlas, one size")
-    shape = tuple(pix_to_face.shape)
-    if len(shape) != 2 or shape[0] != shape[1]:
-        raise ValueError(f"{who} takes (R, R) pix_to_face, got {shape}")
-    R = shape[0]
-    if not 1 <= R <= MAX_SIZE:
-        raise ValueError(f"{who}: render size {R} outside [1, {MAX_SIZE}]")
-    for name, t in (("bary", bary), ("normals", normals)):
-        if tuple(t.shape) != (R, R, 3):
-            raise ValueError(f"{who} takes ({R}, {R}, 3) {name}, got {tuple(t.shape)}")
-    V, T = _mesh_shapes(who, vertices, triangles)
+    R = fragment_size(who, MAX_SIZE, pix_to_face, bary, normals)
+    V, T = mesh_shapes(who, vertices, triangles)
     bake_layout(T, A)
     return R, V, T, A, n_f32, t_f32
 
@@ -173,10 +151,10 @@ def shade_normal_mapped(pix_to_face, bary, normals, vertices, triangles, normal_
     current stream, one launch, no synchronisation; the contract is in include/enarf_nmap.h."""
     import torch
     R, V, T, A, n_f32, t_f32 = check_shade_args(pix_to_face, bary, normals, vertices, triangles, normal_texture, texture)
-    bg = _rgb(background, "shade_normal_mapped", "background")
-    base = _rgb(base_color, "shade_normal_mapped", "base_color")
-    dev = _on_device("shade_normal_mapped", pix_to_face=pix_to_face, bary=bary, normals=normals, vertices=vertices,
-                     triangles=triangles, normal_texture=normal_texture, texture=texture)
+    bg = rgb(background, "shade_normal_mapped", "background")
+    base = rgb(base_color, "shade_normal_mapped", "base_color")
+    dev = on_device("shade_normal_mapped", pix_to_face=pix_to_face, bary=bary, normals=normals, vertices=vertices,
+                    triangles=triangles, normal_texture=normal_texture, texture=texture)
     lib = load()
     keep = [None if t is None else t.contiguous() for t in (pix_to_face, bary, normals, vertices, triangles, normal_texture, texture)]
     ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None

@@ -9,7 +9,7 @@ import ctypes as C
 from collections import namedtuple
 from typing import Optional, Sequence, Tuple
 
-from ._loader import EnarfHipError, Library, device_of, stream_of
+from ._loader import EnarfHipError, Library, device_of, rgb, stream_of
 
 ABI_VERSION = 1
 
@@ -123,17 +123,6 @@ def field_gradient(points, parts, canonical_pose, tri_nchw, feat_cl, mlp_pack, c
     return density, gradient
 
 
-def _rgb(value, name: str) -> Tuple[float, float, float]:
-    """a number or three numbers -> three floats, or ValueError"""
-    try:
-        v = [float(value)] * 3 if not hasattr(value, "__len__") else [float(x) for x in value]
-    except (TypeError, ValueError):
-        raise ValueError(f"ray_normals takes a number or three numbers as {name}, got {value!r}") from None
-    if len(v) != 3:
-        raise ValueError(f"ray_normals takes a number or three numbers as {name}, got {len(v)} values")
-    return v[0], v[1], v[2]
-
-
 def _number(value, name: str) -> float:
     try:
         return float(value)
@@ -201,7 +190,7 @@ def ray_normals(gradient, weights, mask, fallback=None, flags=None, points=None,
     (B, H, W[, 3]). The contract is in include/enarf_nrm.h."""
     import torch
     B, n, Nf = check_ray_args(gradient, weights, mask, fallback, flags, points, shade)
-    bg = _rgb(background, "background")
+    bg = rgb(background, "ray_normals", "background")
     thr, ming = _number(mask_threshold, "mask_threshold"), _number(min_gradient, "min_gradient")
     dev = device_of("ray_normals", (torch.float32,), gradient=gradient, weights=weights, mask=mask, fallback=fallback,
                     points=points)

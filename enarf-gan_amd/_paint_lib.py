@@ -1,7 +1,7 @@
 """ctypes binding of libenarf_paint.so (the C ABI declared in include/enarf_paint.h): deferred shading of the fragment
 buffers rasterize_mesh returns, with a colour or a part label per vertex, on the device.
 
-Loading, return codes and the device-argument checks are `_loader`'s.
+Loading, return codes, the device-argument checks and the shape checks of a mesh and its fragment buffers are `_loader`'s.
 """
 from __future__ import annotations
 
@@ -9,7 +9,7 @@ import ctypes as C
 from collections import namedtuple
 from typing import Tuple
 
-from ._loader import Library, device_of, stream_of
+from ._loader import Library, check_tensors, device_of, fragment_size, mesh_shapes, rgb, stream_of
 
 ABI_VERSION = 1
 
@@ -40,17 +40,6 @@ _library = Library("paint", ABI_VERSION, SIGNATURES, "The deferred shading kerne
 load, check = _library.load, _library.check
 
 
-def _rgb(value, name: str) -> Tuple[float, float, float]:
-    """a number or three numbers -> three floats, or ValueError"""
-    try:
-        v = [float(value)] * 3 if not hasattr(value, "__len__") else [float(x) for x in value]
-    except (TypeError, ValueError):
-        raise ValueError(f"shade_fragments takes a number or three numbers as {name}, got {value!r}") from None
-    if len(v) != 3:
-        raise ValueError(f"shade_fragments takes a number or three numbers as {name}, got {len(v)} values")
-    return v[0], v[1], v[2]
-
-
 def check_shade_args(pix_to_face, bary, normals, vertices, triangles, vertex_colors, vertex_labels, palette
                      ) -> Tuple[int, int, int, int]:
     """(R, V, T, P) of a shade_fragments call (P = 0 in colour mode), or ValueError; shapes and dtypes only, touches no
@@ -68,28 +57,10 @@ def check_shade_args(pix_to_face, bary, normals, vertices, triangles, vertex_col
         if palette is None:
             raise ValueError("shade_fragments: vertex_labels need a (P, 3) palette")
         named.update(vertex_labels=vertex_labels, palette=palette)
-    want = dict(pix_to_face=torch.int64, triangles=torch.int64, vertex_labels=torch.int32)
-    for name, t in named.items():
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"shade_fragments takes tensors; {name} is {type(t).__name__}")
-        if t.dtype != want.get(name, torch.float32):
-            raise ValueError(f"shade_fragments takes {want.get(name, torch.float32)} {name}, got {t.dtype}")
-    shape = tuple(pix_to_face.shape)
-    if len(shape) != 2 or shape[0] != shape[1]:
-        raise ValueError(f"shade_fragments takes (R, R) pix_to_face, got {shape}")
-    R = shape[0]
-    if not 1 <= R <= MAX_SIZE:
-        raise ValueError(f"shade_fragments: render size {R} outside [1, {MAX_SIZE}]")
-    for name in ("bary", "normals"):
-        if tuple(named[name].shape) != (R, R, 3):
-            raise ValueError(f"shade_fragments takes ({R}, {R}, 3) {name}, got {tuple(named[name].shape)}")
-    if vertices.dim() != 2 or vertices.shape[1] != 3:
-        raise ValueError(f"shade_fragments takes (V, 3) vertices, got {tuple(vertices.shape)}")
-    if triangles.dim() != 2 or triangles.shape[1] != 3:
-        raise ValueError(f"shade_fragments takes (T, 3) triangles, got {tuple(triangles.shape)}")
-    V, T = vertices.shape[0], triangles.shape[0]
-    if V >= 2 ** 31 or T >= 2 ** 31:
-        raise ValueError(f"shade_fragments: V = {V}, T = {T}: both must lie in [0, 2^31)")
+    who = "shade_fragments"
+    check_tensors(who, dict(pix_to_face=torch.int64, triangles=torch.int64, vertex_labels=torch.int32), **named)
+    R = fragment_size(who, MAX_SIZE, pix_to_face, bary, normals)
+    V, T = mesh_shapes(who, vertices, triangles)
     P = 0
     if vertex_colors is not None:
         if tuple(vertex_colors.shape) != (V, 3):
@@ -109,7 +80,7 @@ def shade_fragments(pix_to_face, bary, normals, vertices, triangles, vertex_colo
     current stream, one launch, no synchronisation; the contract is in include/enarf_paint.h."""
     import torch
     R, V, T, P = check_shade_args(pix_to_face, bary, normals, vertices, triangles, vertex_colors, vertex_labels, palette)
-    bg, nt = _rgb(background, "background"), _rgb(neutral, "neutral")
+    bg, nt = rgb(background, "shade_fragments", "background"), rgb(neutral, "shade_fragments", "neutral")
     dev = device_of("shade_fragments", (torch.float32, torch.int64, torch.int32), pix_to_face=pix_to_face, bary=bary,
                     normals=normals, vertices=vertices, triangles=triangles, vertex_colors=vertex_colors,
                     vertex_labels=vertex_labels, palette=palette)

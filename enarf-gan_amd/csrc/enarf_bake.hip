@@ -9,12 +9,15 @@
 //                         and optionally the three floats of the unquantised texture.
 //   bake_shade_kernel     one lane per pixel, one launch per image: the fragment's uv from the layout and the stored b',
 //                         four texel loads (one dword each for RGBA8), the bilinear mix as the albedo, and the point,
-//                         light and Phong terms of enarf_paint.hip.
+//                         light and Phong terms of paint_shade_kernel.
 // No atomics, no LDS, no workspace. Everything is fp64 from the stored inputs with FMA contraction off, so the float64
-// restatement of the contract (tests/bake_reference.py) is matched to the rounding of the stored values.
+// restatement of the contract (tests/bake_reference.py) is matched to the rounding of the stored values. The layout, the
+// corners of a cell, the tap and the light and Phong terms are enarf_shade.h's, shared with enarf_paint.hip and
+// enarf_nmap.hip; the point of a texel and the resolve arithmetic are this file's own.
 #include "enarf_bake.h"
 #include "enarf_device.h"
 #include "enarf_host.h"
+#include "enarf_shade.h"
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -23,62 +26,11 @@
 namespace {
 
 using enarf::level;
+using namespace enarf::shade;
 
 constexpr int kBlock = 256;
 constexpr int kMaxR = ENARF_BAKE_MAX_SIZE;
-constexpr long long kMaxCount = 1LL << 31;
-
-struct Layout {
-    int c, n;                                   // cell size in texels, cells a row
-};
-
-// the smallest n >= 1 with 2 n n >= T
-long long cells_needed(long long T) {
-    long long n = (long long)sqrt((double)T / 2.0);
-    if (n < 1) n = 1;
-    while (2 * n * n < T) ++n;
-    while (n > 1 && 2 * (n - 1) * (n - 1) >= T) --n;
-    return n;
-}
-
-// 0 and the layout, or the failure to return
-int find_layout(const char *who, long long T, int A, Layout *out) {
-    if (A < ENARF_BAKE_MIN_ATLAS || A > ENARF_BAKE_MAX_ATLAS)
-        return enarf::host::fail(ENARF_ERR_ARG, "%s: atlas size %d outside [%d, %d]", who, A, ENARF_BAKE_MIN_ATLAS,
-                                 ENARF_BAKE_MAX_ATLAS);
-    if (T < 0 || T >= kMaxCount) return enarf::host::fail(ENARF_ERR_ARG, "%s: T = %lld outside [0, 2^31)", who, T);
-    const long long need = cells_needed(T);
-    const long long c = A / need;
-    if (c < ENARF_BAKE_MIN_CELL)
-        return enarf::host::fail(ENARF_ERR_UNSUPPORTED, "%s: %lld triangles need %lld cells of %d texels a row: an atlas of "
-                                 "at least %lld texels a side, got %d", who, T, need, ENARF_BAKE_MIN_CELL,
-                                 need * ENARF_BAKE_MIN_CELL, A);
-    out->c = (int)c;
-    out->n = A / (int)c;
-    return 0;
-}
-
-// the local corner k of half h, in texels
-__device__ __forceinline__ void corner(int c, int h, int k, int &x, int &y) {
-    if (h == 0) {
-        x = k == 1 ? c - 3 : 1;
-        y = k == 2 ? c - 3 : 1;
-    } else {
-        x = k == 1 ? 3 : c - 1;
-        y = k == 2 ? 3 : c - 1;
-    }
-}
-
-// the three vertex indices of triangle t; false when one of them is outside [0, V)
-__device__ __forceinline__ bool corners_of(const int64_t *triangles, long long t, long long V, long long v[3]) {
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        v[k] = triangles[3 * t + k];
-        ok = ok && v[k] >= 0 && v[k] < V;
-    }
-    return ok;
-}
+constexpr AtlasLimits kLimits = {ENARF_BAKE_MIN_ATLAS, ENARF_BAKE_MAX_ATLAS, ENARF_BAKE_MIN_CELL};
 
 __global__ void __launch_bounds__(kBlock) bake_points_kernel(const enarf_bake_points_args a, const Layout lay) {
 #pragma clang fp contract(off)
@@ -142,39 +94,6 @@ __global__ void __launch_bounds__(kBlock) bake_resolve_kernel(const enarf_bake_r
     }
 }
 
-// c = -N . p / max(|p|, 1e-6) with N = n / max(|n|, 1e-6)
-__device__ __forceinline__ double light_term(const double n[3], const double p[3]) {
-#pragma clang fp contract(off)
-    const double dn = fmax(sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]), 1e-6);
-    const double dp = fmax(sqrt((p[0] * p[0] + p[1] * p[1]) + p[2] * p[2]), 1e-6);
-    const double N0 = n[0] / dn, N1 = n[1] / dn, N2 = n[2] / dn;
-    return -((N0 * p[0] + N1 * p[1]) + N2 * p[2]) / dp;
-}
-
-// texel (0.5 + 0.3 max(c, 0)) + 0.2 max(2 c c - 1, 0)^64
-__device__ __forceinline__ void phong(const double texel[3], double c, double out[3]) {
-#pragma clang fp contract(off)
-    double spec = 0.0;
-    if (c > 0.0) {
-        spec = fmax(2.0 * c * c - 1.0, 0.0);
-#pragma unroll
-        for (int i = 0; i < 6; ++i) spec *= spec;                          // ^64
-    }
-    const double k = 0.5 + 0.3 * (c > 0.0 ? c : 0.0), s = 0.2 * spec;        // a NaN light term counts as 0
-#pragma unroll
-    for (int a = 0; a < 3; ++a) out[a] = texel[a] * k + s;
-}
-
-// one axis of the bilinear tap: the two clamped texel indices and their weights; a NaN coordinate clamps to texel 0
-__device__ __forceinline__ void tap_axis(double u, int A, int &i0, int &i1, double &w0, double &w1) {
-#pragma clang fp contract(off)
-    const double s = u - 0.5, f = floor(s), top = (double)(A - 1);
-    w1 = s - f;
-    w0 = 1.0 - w1;
-    i0 = (int)fmin(fmax(f, 0.0), top);
-    i1 = (int)fmin(fmax(f + 1.0, 0.0), top);
-}
-
 __global__ void __launch_bounds__(kBlock) bake_shade_kernel(const enarf_bake_shade_args a, const Layout lay) {
 #pragma clang fp contract(off)
     const long long p = (long long)blockIdx.x * kBlock + threadIdx.x;
@@ -200,29 +119,9 @@ __global__ void __launch_bounds__(kBlock) bake_shade_kernel(const enarf_bake_sha
         }
         const double u = ((double)b0 * (double)ux[0] + (double)b1 * (double)ux[1]) + (double)b2 * (double)ux[2];
         const double w = ((double)b0 * (double)uy[0] + (double)b1 * (double)uy[1]) + (double)b2 * (double)uy[2];
-        int x0, x1, y0, y1;
-        double wx0, wx1, wy0, wy1;
-        tap_axis(u, a.A, x0, x1, wx0, wx1);
-        tap_axis(w, a.A, y0, y1, wy0, wy1);
-        const double w00 = wx0 * wy0, w01 = wx1 * wy0, w10 = wx0 * wy1, w11 = wx1 * wy1;
-        const long long e00 = (long long)y0 * a.A + x0, e01 = (long long)y0 * a.A + x1;
-        const long long e10 = (long long)y1 * a.A + x0, e11 = (long long)y1 * a.A + x1;
-        if (a.texture) {
-            const uint32_t *tex = reinterpret_cast<const uint32_t *>(a.texture);
-            const uint32_t t00 = tex[e00], t01 = tex[e01], t10 = tex[e10], t11 = tex[e11];
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) {
-                const int s = 8 * ch;
-                texel[ch] = ((w00 * ((double)((t00 >> s) & 255u) / 255.0) + w01 * ((double)((t01 >> s) & 255u) / 255.0)) +
-                             w10 * ((double)((t10 >> s) & 255u) / 255.0)) + w11 * ((double)((t11 >> s) & 255u) / 255.0);
-            }
-        } else {
-            const float *tex = a.texture_f32;
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch)
-                texel[ch] = ((w00 * (double)tex[3 * e00 + ch] + w01 * (double)tex[3 * e01 + ch]) +
-                             w10 * (double)tex[3 * e10 + ch]) + w11 * (double)tex[3 * e11 + ch];
-        }
+        const Tap tp = tap_at(u, w, a.A);
+        if (a.texture) tap_rgba8(a.texture, tp, 1.0, 0.0, texel);
+        else tap_f32(a.texture_f32, tp, texel);
         if (a.lit) {
             const float *q0 = a.vertices + 3 * v[0], *q1 = a.vertices + 3 * v[1], *q2 = a.vertices + 3 * v[2];
             double nn[3], pt[3];
@@ -245,8 +144,6 @@ __global__ void __launch_bounds__(kBlock) bake_shade_kernel(const enarf_bake_sha
     }
 }
 
-unsigned blocks(long long count) { return (unsigned)((count + kBlock - 1) / kBlock); }
-
 }  // namespace
 
 extern "C" {
@@ -257,7 +154,7 @@ const char *enarf_bake_last_error(void) { return enarf::host::last_error(); }
 
 int enarf_bake_layout(int64_t T, int32_t A, int32_t *cell, int32_t *cells_per_row) {
     Layout lay;
-    if (const int rc = find_layout("enarf_bake_layout", (long long)T, A, &lay)) return rc;
+    if (const int rc = find_layout("enarf_bake_layout", (long long)T, A, kLimits, &lay)) return rc;
     if (cell) *cell = lay.c;
     if (cells_per_row) *cells_per_row = lay.n;
     return 0;
@@ -269,13 +166,13 @@ int enarf_bake_points(const enarf_bake_points_args *args, void *stream) {
     const enarf_bake_points_args &a = *args;
     if (a.V < 0 || a.V >= kMaxCount) return enarf::host::fail(ENARF_ERR_ARG, "%s: V = %lld outside [0, 2^31)", who, (long long)a.V);
     Layout lay;
-    if (const int rc = find_layout(who, (long long)a.T, a.A, &lay)) return rc;
+    if (const int rc = find_layout(who, (long long)a.T, a.A, kLimits, &lay)) return rc;
     if (a.row0 < 0 || a.rows < 1 || (long long)a.row0 + a.rows > a.A)
         return enarf::host::fail(ENARF_ERR_ARG, "%s: rows [%d, %d + %d) outside the atlas of %d rows", who, a.row0, a.row0,
                                  a.rows, a.A);
     if (!a.points || !a.texel_face || (a.V > 0 && !a.vertices) || (a.T > 0 && !a.triangles))
         return enarf::host::fail(ENARF_ERR_ARG, "%s: null points, texel_face, vertices or triangles", who);
-    hipLaunchKernelGGL(bake_points_kernel, dim3(blocks((long long)a.rows * a.A)), dim3(kBlock), 0,
+    hipLaunchKernelGGL(bake_points_kernel, dim3(blocks((long long)a.rows * a.A, kBlock)), dim3(kBlock), 0,
                        static_cast<hipStream_t>(stream), a, lay);
     return enarf::host::check_launch("enarf_bake_points: bake_points_kernel");
 }
@@ -294,7 +191,7 @@ int enarf_bake_resolve(const enarf_bake_resolve_args *args, void *stream) {
     if (!a.texel_face || !a.texture) return enarf::host::fail(ENARF_ERR_ARG, "%s: null texel_face or texture", who);
     if (reinterpret_cast<uintptr_t>(a.texture) & 3u)
         return enarf::host::fail(ENARF_ERR_ARG, "%s: the texture is written one 32-bit texel at a time: 4-byte alignment", who);
-    hipLaunchKernelGGL(bake_resolve_kernel, dim3(blocks(a.count)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(bake_resolve_kernel, dim3(blocks(a.count, kBlock)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), a);
     return enarf::host::check_launch("enarf_bake_resolve: bake_resolve_kernel");
 }
 
@@ -305,14 +202,14 @@ int enarf_bake_shade(const enarf_bake_shade_args *args, void *stream) {
     if (a.R < 1 || a.R > kMaxR) return enarf::host::fail(ENARF_ERR_ARG, "%s: render size %d outside [1, %d]", who, a.R, kMaxR);
     if (a.V < 0 || a.V >= kMaxCount) return enarf::host::fail(ENARF_ERR_ARG, "%s: V = %lld outside [0, 2^31)", who, (long long)a.V);
     Layout lay;
-    if (const int rc = find_layout(who, (long long)a.T, a.A, &lay)) return rc;
+    if (const int rc = find_layout(who, (long long)a.T, a.A, kLimits, &lay)) return rc;
     if ((a.texture != nullptr) == (a.texture_f32 != nullptr))
         return enarf::host::fail(ENARF_ERR_ARG, "%s: exactly one of texture and texture_f32 must be given", who);
     if (reinterpret_cast<uintptr_t>(a.texture) & 3u)
         return enarf::host::fail(ENARF_ERR_ARG, "%s: the texture is read one 32-bit texel at a time: 4-byte alignment", who);
     if (!a.pix_to_face || !a.bary || !a.normals || !a.image || (a.V > 0 && !a.vertices) || (a.T > 0 && !a.triangles))
         return enarf::host::fail(ENARF_ERR_ARG, "%s: null pix_to_face, bary, normals, image, vertices or triangles", who);
-    hipLaunchKernelGGL(bake_shade_kernel, dim3(blocks((long long)a.R * a.R)), dim3(kBlock), 0,
+    hipLaunchKernelGGL(bake_shade_kernel, dim3(blocks((long long)a.R * a.R, kBlock)), dim3(kBlock), 0,
                        static_cast<hipStream_t>(stream), a, lay);
     return enarf::host::check_launch("enarf_bake_shade: bake_shade_kernel");
 }

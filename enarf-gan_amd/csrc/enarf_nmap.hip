@@ -7,13 +7,15 @@
 //   nmap_shade_kernel    one lane per pixel, one launch per image: the fragment's uv from the layout and the stored b',
 //                        four texel loads of the normal map and four of the albedo (one dword each for RGBA8), the frame
 //                        of the face from the vertices of this call, the shading normal, and the point, light and Phong
-//                        terms of enarf_paint.hip.
+//                        terms of paint_shade_kernel.
 // No atomics, no LDS, no workspace. Everything is fp64 from the stored inputs with FMA contraction off, so the float64
 // restatement of the contract (tests/nmap_reference.py) is matched to the rounding of the stored values. The layout, the
-// tap and the light terms restate enarf_bake.hip's: a library's kernels and helpers are its own.
+// corners of a cell, the tap and the light and Phong terms are enarf_shade.h's, the definitions enarf_bake.hip bakes and
+// shades with; the frame of a face and the encoding of a channel are this file's own.
 #include "enarf_nmap.h"
 #include "enarf_device.h"
 #include "enarf_host.h"
+#include "enarf_shade.h"
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -22,74 +24,11 @@
 namespace {
 
 using enarf::level;
+using namespace enarf::shade;
 
 constexpr int kBlock = 256;
 constexpr int kMaxR = ENARF_NMAP_MAX_SIZE;
-constexpr long long kMaxCount = 1LL << 31;
-
-struct Layout {
-    int c, n;                                   // cell size in texels, cells a row
-};
-
-// the smallest n >= 1 with 2 n n >= T
-long long cells_needed(long long T) {
-    long long n = (long long)sqrt((double)T / 2.0);
-    if (n < 1) n = 1;
-    while (2 * n * n < T) ++n;
-    while (n > 1 && 2 * (n - 1) * (n - 1) >= T) --n;
-    return n;
-}
-
-// 0 and the layout of enarf_bake.h, or the failure to return
-int find_layout(const char *who, long long T, int A, Layout *out) {
-    if (A < ENARF_NMAP_MIN_ATLAS || A > ENARF_NMAP_MAX_ATLAS)
-        return enarf::host::fail(ENARF_ERR_ARG, "%s: atlas size %d outside [%d, %d]", who, A, ENARF_NMAP_MIN_ATLAS,
-                                 ENARF_NMAP_MAX_ATLAS);
-    if (T < 0 || T >= kMaxCount) return enarf::host::fail(ENARF_ERR_ARG, "%s: T = %lld outside [0, 2^31)", who, T);
-    const long long need = cells_needed(T);
-    const long long c = A / need;
-    if (c < ENARF_NMAP_MIN_CELL)
-        return enarf::host::fail(ENARF_ERR_UNSUPPORTED, "%s: %lld triangles need %lld cells of %d texels a row: an atlas of "
-                                 "at least %lld texels a side, got %d", who, T, need, ENARF_NMAP_MIN_CELL,
-                                 need * ENARF_NMAP_MIN_CELL, A);
-    out->c = (int)c;
-    out->n = A / (int)c;
-    return 0;
-}
-
-// the local corner k of half h, in texels
-__device__ __forceinline__ void corner(int c, int h, int k, int &x, int &y) {
-    if (h == 0) {
-        x = k == 1 ? c - 3 : 1;
-        y = k == 2 ? c - 3 : 1;
-    } else {
-        x = k == 1 ? 3 : c - 1;
-        y = k == 2 ? 3 : c - 1;
-    }
-}
-
-// the three vertex indices of triangle t; false when one of them is outside [0, V)
-__device__ __forceinline__ bool corners_of(const int64_t *triangles, long long t, long long V, long long v[3]) {
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        v[k] = triangles[3 * t + k];
-        ok = ok && v[k] >= 0 && v[k] < V;
-    }
-    return ok;
-}
-
-__device__ __forceinline__ double length3(const double a[3]) {
-#pragma clang fp contract(off)
-    return sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);
-}
-
-__device__ __forceinline__ void cross3(const double a[3], const double b[3], double out[3]) {
-#pragma clang fp contract(off)
-    out[0] = a[1] * b[2] - a[2] * b[1];
-    out[1] = a[2] * b[0] - a[0] * b[2];
-    out[2] = a[0] * b[1] - a[1] * b[0];
-}
+constexpr AtlasLimits kLimits = {ENARF_NMAP_MIN_ATLAS, ENARF_NMAP_MAX_ATLAS, ENARF_NMAP_MIN_CELL};
 
 __device__ __forceinline__ bool positive_finite(double x) { return x > 0.0 && x < (double)INFINITY; }
 
@@ -155,59 +94,6 @@ __global__ void __launch_bounds__(kBlock) nmap_encode_kernel(const enarf_nmap_en
     }
 }
 
-// texel (0.5 + 0.3 max(c, 0)) + 0.2 max(2 c c - 1, 0)^64
-__device__ __forceinline__ void phong(const double texel[3], double c, double out[3]) {
-#pragma clang fp contract(off)
-    double spec = 0.0;
-    if (c > 0.0) {
-        spec = fmax(2.0 * c * c - 1.0, 0.0);
-#pragma unroll
-        for (int i = 0; i < 6; ++i) spec *= spec;                          // ^64
-    }
-    const double k = 0.5 + 0.3 * (c > 0.0 ? c : 0.0), s = 0.2 * spec;        // a NaN light term counts as 0
-#pragma unroll
-    for (int a = 0; a < 3; ++a) out[a] = texel[a] * k + s;
-}
-
-// one axis of the bilinear tap: the two clamped texel indices and their weights; a NaN coordinate clamps to texel 0
-__device__ __forceinline__ void tap_axis(double u, int A, int &i0, int &i1, double &w0, double &w1) {
-#pragma clang fp contract(off)
-    const double s = u - 0.5, f = floor(s), top = (double)(A - 1);
-    w1 = s - f;
-    w0 = 1.0 - w1;
-    i0 = (int)fmin(fmax(f, 0.0), top);
-    i1 = (int)fmin(fmax(f + 1.0, 0.0), top);
-}
-
-struct Tap {
-    long long e[4];                             // y0 x0, y0 x1, y1 x0, y1 x1
-    double w[4];
-};
-
-// the tap of an RGBA8 texture; scale and shift decode a byte: (scale byte) / 255 - shift
-__device__ __forceinline__ void tap_rgba8(const uint8_t *texture, const Tap &tp, double scale, double shift, double out[3]) {
-#pragma clang fp contract(off)
-    const uint32_t *tex = reinterpret_cast<const uint32_t *>(texture);
-    const uint32_t t0 = tex[tp.e[0]], t1 = tex[tp.e[1]], t2 = tex[tp.e[2]], t3 = tex[tp.e[3]];
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-        const int s = 8 * ch;
-        const double d0 = (scale * (double)((t0 >> s) & 255u)) / 255.0 - shift;
-        const double d1 = (scale * (double)((t1 >> s) & 255u)) / 255.0 - shift;
-        const double d2 = (scale * (double)((t2 >> s) & 255u)) / 255.0 - shift;
-        const double d3 = (scale * (double)((t3 >> s) & 255u)) / 255.0 - shift;
-        out[ch] = ((tp.w[0] * d0 + tp.w[1] * d1) + tp.w[2] * d2) + tp.w[3] * d3;
-    }
-}
-
-__device__ __forceinline__ void tap_f32(const float *tex, const Tap &tp, double out[3]) {
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch)
-        out[ch] = ((tp.w[0] * (double)tex[3 * tp.e[0] + ch] + tp.w[1] * (double)tex[3 * tp.e[1] + ch]) +
-                   tp.w[2] * (double)tex[3 * tp.e[2] + ch]) + tp.w[3] * (double)tex[3 * tp.e[3] + ch];
-}
-
 __global__ void __launch_bounds__(kBlock) nmap_shade_kernel(const enarf_nmap_shade_args a, const Layout lay) {
 #pragma clang fp contract(off)
     const long long p = (long long)blockIdx.x * kBlock + threadIdx.x;
@@ -236,14 +122,7 @@ __global__ void __launch_bounds__(kBlock) nmap_shade_kernel(const enarf_nmap_sha
         }
         const double u = ((double)b0 * (double)ux[0] + (double)b1 * (double)ux[1]) + (double)b2 * (double)ux[2];
         const double w = ((double)b0 * (double)uy[0] + (double)b1 * (double)uy[1]) + (double)b2 * (double)uy[2];
-        int x0, x1, y0, y1;
-        double wx0, wx1, wy0, wy1;
-        tap_axis(u, a.A, x0, x1, wx0, wx1);
-        tap_axis(w, a.A, y0, y1, wy0, wy1);
-        Tap tp;
-        tp.w[0] = wx0 * wy0, tp.w[1] = wx1 * wy0, tp.w[2] = wx0 * wy1, tp.w[3] = wx1 * wy1;
-        tp.e[0] = (long long)y0 * a.A + x0, tp.e[1] = (long long)y0 * a.A + x1;
-        tp.e[2] = (long long)y1 * a.A + x0, tp.e[3] = (long long)y1 * a.A + x1;
+        const Tap tp = tap_at(u, w, a.A);
         if (a.texture) {
             tap_rgba8(a.texture, tp, 1.0, 0.0, texel);
         } else if (a.texture_f32) {
@@ -271,7 +150,7 @@ __global__ void __launch_bounds__(kBlock) nmap_shade_kernel(const enarf_nmap_sha
             } else {
 #pragma unroll
                 for (int k = 0; k < 3; ++k) ns[k] = (double)a.normals[3 * p + k];
-                const double dn = fmax(length3(ns), 1e-6);
+                const double dn = floored_length(ns);
 #pragma unroll
                 for (int k = 0; k < 3; ++k) unit[k] = ns[k] / dn;
             }
@@ -282,8 +161,7 @@ __global__ void __launch_bounds__(kBlock) nmap_shade_kernel(const enarf_nmap_sha
 #pragma unroll
             for (int k = 0; k < 3; ++k)
                 pt[k] = ((double)b0 * (double)q0[k] + (double)b1 * (double)q1[k]) + (double)b2 * (double)q2[k];
-            const double dp = fmax(length3(pt), 1e-6);
-            phong(texel, -((unit[0] * pt[0] + unit[1] * pt[1]) + unit[2] * pt[2]) / dp, shaded);
+            phong(texel, facing(unit, pt, floored_length(pt)), shaded);
         } else {
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) shaded[ch] = texel[ch];
@@ -297,8 +175,6 @@ __global__ void __launch_bounds__(kBlock) nmap_shade_kernel(const enarf_nmap_sha
         a.image[3 * p + ch] = level(shaded[ch]);
     }
 }
-
-unsigned blocks(long long count) { return (unsigned)((count + kBlock - 1) / kBlock); }
 
 }  // namespace
 
@@ -324,7 +200,7 @@ int enarf_nmap_encode(const enarf_nmap_encode_args *args, void *stream) {
         return enarf::host::fail(ENARF_ERR_ARG, "%s: null texel_face, vectors, texture, vertices or triangles", who);
     if (reinterpret_cast<uintptr_t>(a.texture) & 3u)
         return enarf::host::fail(ENARF_ERR_ARG, "%s: the texture is written one 32-bit texel at a time: 4-byte alignment", who);
-    hipLaunchKernelGGL(nmap_encode_kernel, dim3(blocks(a.count)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(nmap_encode_kernel, dim3(blocks(a.count, kBlock)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), a);
     return enarf::host::check_launch("enarf_nmap_encode: nmap_encode_kernel");
 }
 
@@ -335,7 +211,7 @@ int enarf_nmap_shade(const enarf_nmap_shade_args *args, void *stream) {
     if (a.R < 1 || a.R > kMaxR) return enarf::host::fail(ENARF_ERR_ARG, "%s: render size %d outside [1, %d]", who, a.R, kMaxR);
     if (a.V < 0 || a.V >= kMaxCount) return enarf::host::fail(ENARF_ERR_ARG, "%s: V = %lld outside [0, 2^31)", who, (long long)a.V);
     Layout lay;
-    if (const int rc = find_layout(who, (long long)a.T, a.A, &lay)) return rc;
+    if (const int rc = find_layout(who, (long long)a.T, a.A, kLimits, &lay)) return rc;
     if ((a.normal_texture != nullptr) == (a.normal_texture_f32 != nullptr))
         return enarf::host::fail(ENARF_ERR_ARG, "%s: exactly one of normal_texture and normal_texture_f32 must be given", who);
     if (a.texture && a.texture_f32)
@@ -344,7 +220,7 @@ int enarf_nmap_shade(const enarf_nmap_shade_args *args, void *stream) {
         return enarf::host::fail(ENARF_ERR_ARG, "%s: an RGBA8 texture is read one 32-bit texel at a time: 4-byte alignment", who);
     if (!a.pix_to_face || !a.bary || !a.normals || !a.image || (a.V > 0 && !a.vertices) || (a.T > 0 && !a.triangles))
         return enarf::host::fail(ENARF_ERR_ARG, "%s: null pix_to_face, bary, normals, image, vertices or triangles", who);
-    hipLaunchKernelGGL(nmap_shade_kernel, dim3(blocks((long long)a.R * a.R)), dim3(kBlock), 0,
+    hipLaunchKernelGGL(nmap_shade_kernel, dim3(blocks((long long)a.R * a.R, kBlock)), dim3(kBlock), 0,
                        static_cast<hipStream_t>(stream), a, lay);
     return enarf::host::check_launch("enarf_nmap_shade: nmap_shade_kernel");
 }

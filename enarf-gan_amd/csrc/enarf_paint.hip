@@ -8,10 +8,12 @@
 //                        output is a function of the inputs alone. Background pixels read nothing through their face id,
 //                        so a wave over background costs three loads and the stores.
 // Everything is fp64 from the fp32 inputs with FMA contraction off, as in enarf_raster.hip, so the float64 restatement
-// of the contract (tests/paint_reference.py) is matched to the rounding of the stored fp32.
+// of the contract (tests/paint_reference.py) is matched to the rounding of the stored fp32. The corners of a face and
+// the light and Phong terms are enarf_shade.h's, which the textured shades (enarf_bake.hip, enarf_nmap.hip) use too.
 #include "enarf_paint.h"
 #include "enarf_device.h"
 #include "enarf_host.h"
+#include "enarf_shade.h"
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -20,10 +22,10 @@
 namespace {
 
 using enarf::level;
+using namespace enarf::shade;
 
 constexpr int kBlock = 256;
 constexpr int kMaxR = ENARF_PAINT_MAX_SIZE;
-constexpr long long kMaxCount = 1LL << 31;
 
 // the corner of the largest stored b', compared as fp32: a later corner wins only when strictly larger
 __device__ __forceinline__ int top_corner(float b0, float b1, float b2) {
@@ -34,43 +36,13 @@ __device__ __forceinline__ int top_corner(float b0, float b1, float b2) {
     return k;
 }
 
-// c = -N . p / max(|p|, 1e-6) with N = n / max(|n|, 1e-6)
-__device__ __forceinline__ double light_term(const double n[3], const double p[3]) {
-#pragma clang fp contract(off)
-    const double dn = fmax(sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]), 1e-6);
-    const double dp = fmax(sqrt((p[0] * p[0] + p[1] * p[1]) + p[2] * p[2]), 1e-6);
-    const double N0 = n[0] / dn, N1 = n[1] / dn, N2 = n[2] / dn;
-    return -((N0 * p[0] + N1 * p[1]) + N2 * p[2]) / dp;
-}
-
-// texel (0.5 + 0.3 max(c, 0)) + 0.2 max(2 c c - 1, 0)^64
-__device__ __forceinline__ void phong(const double texel[3], double c, double out[3]) {
-#pragma clang fp contract(off)
-    double spec = 0.0;
-    if (c > 0.0) {
-        spec = fmax(2.0 * c * c - 1.0, 0.0);
-#pragma unroll
-        for (int i = 0; i < 6; ++i) spec *= spec;                          // ^64
-    }
-    const double k = 0.5 + 0.3 * (c > 0.0 ? c : 0.0), s = 0.2 * spec;        // a NaN light term counts as 0
-#pragma unroll
-    for (int a = 0; a < 3; ++a) out[a] = texel[a] * k + s;
-}
-
 __global__ void __launch_bounds__(kBlock) paint_shade_kernel(const enarf_paint_shade_args a) {
 #pragma clang fp contract(off)
     const long long p = (long long)blockIdx.x * kBlock + threadIdx.x;
     if (p >= (long long)a.R * a.R) return;
     const long long f = a.pix_to_face[p];
     long long v[3] = {0, 0, 0};
-    bool drawn = f >= 0 && f < a.T;
-    if (drawn) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            v[k] = a.triangles[3 * f + k];
-            drawn = drawn && v[k] >= 0 && v[k] < a.V;
-        }
-    }
+    const bool drawn = f >= 0 && f < a.T && corners_of(a.triangles, f, a.V, v);
     double texel[3], shaded[3];
     if (!drawn) {
 #pragma unroll
@@ -134,8 +106,7 @@ int enarf_paint_shade(const enarf_paint_shade_args *args, void *stream) {
         return enarf::host::fail(ENARF_ERR_ARG, "%s: label mode takes a palette of P >= 1 entries, got P = %d", who, a.P);
     if (!a.pix_to_face || !a.bary || !a.normals || !a.image || (a.V > 0 && !a.vertices) || (a.T > 0 && !a.triangles))
         return enarf::host::fail(ENARF_ERR_ARG, "%s: null pix_to_face, bary, normals, image, vertices or triangles", who);
-    const long long npx = (long long)a.R * a.R;
-    hipLaunchKernelGGL(paint_shade_kernel, dim3((unsigned)((npx + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+    hipLaunchKernelGGL(paint_shade_kernel, dim3(blocks((long long)a.R * a.R, kBlock)), dim3(kBlock), 0,
                        static_cast<hipStream_t>(stream), a);
     return enarf::host::check_launch("enarf_paint_shade: paint_shade_kernel");
 }

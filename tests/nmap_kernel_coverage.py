@@ -11,6 +11,7 @@ NMAP_KERNEL_TESTS = {
         "test_gpu_nmap::test_bake_normal_map_is_its_launches_by_hand"],
     f"{_NS}nmap_shade_kernel(enarf_nmap_shade_args, {_NS}Layout)": [
         "test_gpu_nmap::test_hand_written_fragments_match_the_referee",
+        "test_gpu_nmap::test_unlit_normal_mapped_shade_equals_shade_textured_bit_for_bit",
         "test_gpu_nmap::test_the_normal_mapped_sphere_matches_the_referee",
         "test_gpu_nmap::test_a_constant_field_round_trips_on_the_device",
         "test_gpu_nmap::test_a_flat_map_gives_the_face_normal"],

@@ -155,6 +155,25 @@ def test_hand_written_fragments_match_the_referee():
     assert (got["albedo"][2, 0] == 1).all()                                                     # the default base colour
 
 
+def test_unlit_normal_mapped_shade_equals_shade_textured_bit_for_bit():
+    """nmap_shade_kernel and bake_shade_kernel find a fragment's texels through the one definition in csrc/enarf_shade.h
+    (layout, uv, tap): on the 8 x 8 hand-written buffer, with the RGBA8 and the fp32 16 x 16 texture, an unlit
+    shade_normal_mapped returns the image, albedo and shaded of shade_textured, bit for bit"""
+    from enarf_gan_amd import ops
+    h = PC.hand_buffer()
+    geo = [_dev(h[k]) for k in GEO]
+    nmap = _dev(NC.hand_normal_textures(16)[0])
+    for tex in BC.hand_textures(16):
+        kw = dict(lit=False, background=(0.1, 0.2, 0.3))
+        mapped = ops.shade_normal_mapped(*geo, nmap, texture=_dev(tex), **kw)
+        plain = ops.shade_textured(*geo, _dev(tex), **kw)
+        torch.cuda.synchronize()
+        for k in ("image", "albedo", "shaded"):
+            a, b = _np(getattr(mapped, k)), _np(getattr(plain, k))
+            print(f"{tex.dtype} texture, {k}: {(a.view(np.uint8) != b.view(np.uint8)).sum()} bytes differ")
+            assert a.dtype == b.dtype and a.shape == b.shape == (8, 8, 3) and a.tobytes() == b.tobytes(), (tex.dtype, k)
+
+
 def test_the_normal_mapped_sphere_matches_the_referee():
     """the rasterised sphere (R = 257: a partial last wavefront) at the atlas size tests/test_gpu_bake.py uses (510): random
     normal maps of both kinds x {RGBA8 albedo, fp32 albedo, constant}, lit and not, every pixel"""
